@@ -402,7 +402,28 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="no kernels and no GPU: exercises launcher, rendezvous, barrier, MAX over ranks "
                          "and the JSON line (value is null); what the CPU tests run")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's (u, v) of the LAST timed step as DIR/u.npy and DIR/v.npy "
+                         "(float32, rows of the [pairs x rows, cols] stack; a fixed seeded sample of rows when all of "
+                         "them would exceed 64 MB), so that two builds can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs: everything written, npy headers included
+DUMP_SEED = 0x5EED0D          # --dump-outputs: the row sample is the same in every run
+
+
+def dump_rows(n_rows, row_bytes, n_arrays):
+    """Row indices (sorted) that --dump-outputs keeps of `n_arrays` stacks of `n_rows` rows: all of them when they fit in
+    DUMP_MAX_BYTES, else a fixed seeded sample of as many rows as fit."""
+    import numpy as np
+    keep = (DUMP_MAX_BYTES - n_arrays * 256) // (n_arrays * row_bytes)
+    if keep >= n_rows:
+        return np.arange(n_rows)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=keep, replace=False))
 
 
 def _free_port():
@@ -675,6 +696,18 @@ def main(argv=None):
     for _ in range(args.warmup):
         step()
     dt, per_rank = timed(args.steps)
+
+    if args.dump_outputs and rank == 0:
+        # the buffers the last timed step wrote, taken before anything below runs the path again
+        if args.mode == "rowshard":
+            fields = [t[:, a0:b0] for t in (u, v)]  # rank 0's row band
+        else:
+            fields = lanes[(counter[0] - 1) % F][2]
+        flat = [t.reshape(-1, COLS) for t in fields]
+        idx = torch.from_numpy(dump_rows(flat[0].shape[0], COLS * 4, len(flat))).to(dev)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in zip(("u", "v"), flat):
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), t.index_select(0, idx).cpu().numpy())
 
     # the same code path for >= --sustained-s seconds back to back: clocks under sustained load
     sustained = None

@@ -85,6 +85,22 @@ def test_byte_model_matches_baseline_md():
     assert b.level0_kernel_bytes_pair(1080, 1920, 5) == 16 * 2073600 + 8 * 518400
 
 
+def test_bench_dump_rows_are_fixed_and_fit_the_budget():
+    """--dump-outputs keeps every row when they fit in 64 MB, else the same seeded sample of rows in every run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert np.array_equal(b.dump_rows(1080, 1920 * 4, 2), np.arange(1080))
+    rows = b.dump_rows(8 * 1080, 1920 * 4, 2)
+    assert np.array_equal(rows, b.dump_rows(8 * 1080, 1920 * 4, 2))
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 8 * 1080
+    assert 2 * (len(rows) * 1920 * 4 + 128) <= 64 * 10**6 < 2 * ((len(rows) + 1) * 1920 * 4 + 128)
+    assert b.parse_args(["--steps", "7", "--dump-outputs", "d"]).steps == 7
+    with pytest.raises(SystemExit):
+        b.parse_args(["--steps", "0"])
+
+
 def test_bench_gpus_n_launches_n_ranks():
     """`python bench.py --gpus 2` run directly (no torchrun environment) must start 2 ranks itself:
     the launcher spawns torch.distributed.run as a child and relays rank 0's JSON line.  --dry-run

@@ -230,6 +230,40 @@ def test_lk_pyr_1080p_bench_pairs_bit_exact(mods):
         assert np.array_equal(host(gu[i]), eu) and np.array_equal(host(gv[i]), ev)
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the last timed step's (u, v) rows, the same bits in two runs whose last steps ran on
+    different passes in flight (3 and 4 steps), and pair 0's rows equal to the oracle's flow of the first bench pair."""
+    import importlib.util
+    import json
+    import subprocess
+    import sys
+    from introtocomputervision_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MICV_BENCH_FORCE_DIST")}
+    dumps = []
+    for steps in (3, 4):
+        out = tmp_path / f"s{steps}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "1",
+                            "--preroll-s", "0", "--sustained-s", "0", "--cpu-pairs", "0", "--no-profile-pass", "--no-pmc",
+                            "--no-secondary", "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["config"]["flow_check"]["ok"]
+        assert sorted(os.listdir(out)) == ["u.npy", "v.npy"]
+        assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 * 10**6
+        dumps.append((np.load(out / "u.npy"), np.load(out / "v.npy")))
+    rows = b.dump_rows(b.ROWS * 8, b.COLS * 4, 2)
+    for a, c in zip(*dumps):
+        assert a.dtype == np.float32 and a.shape == (len(rows), b.COLS) and np.array_equal(a, c)
+    eu, ev = orc.lk_flow_pyr(*synth.lk_pair(0x5EED0005, b.ROWS, b.COLS, 3, -2), b.WIN, b.LEVELS)
+    first = rows < b.ROWS
+    assert first.any()
+    assert np.array_equal(dumps[0][0][first], eu[rows[first]]) and np.array_equal(dumps[0][1][first], ev[rows[first]])
+
+
 def test_bad_arguments(mods):
     lk, pyr = mods
     from introtocomputervision_amd._capi import MicvError
