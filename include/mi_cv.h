@@ -421,7 +421,10 @@ int micv_sift_descriptors_host(micv_ctx *ctx, const float *gx, const float *gy, 
 #define MICV_STEREO_MIN_SSD_5E6 2 /* leave -1 where best SSD >= 5e6, DisparitySSD.cu:16 */
 #define MICV_STEREO_SERIAL      4 /* serial::disparitySSD as written (DisparitySSD.cpp:35-61):
                                      per-term round() into an int sum, search clamped to the padded
-                                     image, best = (99999999, 0) initially.  SSD only. */
+                                     image, best = (99999999, 0) initially.  SSD only, and alone:
+                                     with COLS_2R, MIN_SSD_5E6 or ROLLING the call fails with
+                                     MICV_EINVAL before anything runs (the function has a (2r+1)^2
+                                     window and no threshold). */
 #define MICV_STEREO_ROLLING     8 /* column sums as the CUDA kernels keep them (DisparitySSD.cu:97-138,
                                      DisparityNCorr.cu:117-173): strips of ROWS_PER_THREAD = 40 rows;
                                      a strip's first row sums its 2r+1 terms top -> bottom from 0, each

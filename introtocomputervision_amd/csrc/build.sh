@@ -36,7 +36,8 @@ echo "built $out"
 # its wait before its first use; no compiler-placed LDS / scalar-memory operation inside a COUNTED wait's window).  When
 # it fails -- a compiler upgrade that reloads taps inside a counted window would give wrong window sums, not a build
 # error -- the two files that use counted waits are rebuilt with the single-wait column pass (-DMICV_LK_COL_FULLWAIT,
-# ~1 % slower) and audited again.  (The CPU test suite runs the same audit; this is for builds that ship without it.)
+# ~1 % slower) and audited again; a finding in stereo_exact.hip's scalar look-ahead has no such fallback and fails that
+# second audit too.  (The CPU test suite runs the same audit; this is for builds that ship without it.)
 if [[ -n "${MICV_AUDIT:-}" && -z "${MICV_AUDIT_DONE:-}" ]]; then
   audit="$here/../../tools/audit_asm_loads.py"
   if ! python3 "$audit" ${EXTRA_HIPCC_FLAGS:-}; then

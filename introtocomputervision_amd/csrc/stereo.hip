@@ -251,6 +251,9 @@ static int stereo_common(const char *fn, micv_ctx *ctx, const float *left, const
     MICV_REQUIRE(!(ncc && (flags & MICV_STEREO_SERIAL)), "%s: SERIAL applies to SSD only", fn);
     MICV_REQUIRE(!((flags & MICV_STEREO_SERIAL) && (flags & MICV_STEREO_ROLLING)),
                  "%s: SERIAL and ROLLING describe different reference functions", fn);
+    MICV_REQUIRE(!((flags & MICV_STEREO_SERIAL) && (flags & (MICV_STEREO_COLS_2R | MICV_STEREO_MIN_SSD_5E6))),
+                 "%s: SERIAL takes neither COLS_2R nor MIN_SSD_5E6 (serial::disparitySSD has a (2r+1)^2 window and no "
+                 "threshold)", fn);
     MICV_REQUIRE(!((flags & MICV_STEREO_COLS_2R) && rad == 0), "%s: COLS_2R needs radius >= 1", fn);
     MICV_HIP(hipSetDevice(ctx->device));
     StereoArgs a;

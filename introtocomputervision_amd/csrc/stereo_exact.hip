@@ -72,13 +72,8 @@ __device__ __forceinline__ uint32_t sx_colsum(const uint32_t (&l)[NG], const uin
     uint32_t acc = 0;
 #pragma unroll
     for (int g = f0; g <= f1; g++) acc = __builtin_amdgcn_udot4(l[g], r[g], acc, false);
-#ifdef MICV_SX_NOMASK  // timing experiment only (wrong sums): what the scalar masks cost
-    if (g0 < f0) acc = __builtin_amdgcn_udot4(l[(g0 + (k0 & 3)) % NG], r[g0], acc, false);
-    if (g1 > f1) acc = __builtin_amdgcn_udot4(l[(g1 + 1 + (k1 & 3)) % NG], r[g1], acc, false);
-#else
     if (g0 < f0) acc = __builtin_amdgcn_udot4(l[g0] & (0xFFFFFFFFu << (8 * (k0 & 3))), r[g0], acc, false);
     if (g1 > f1) acc = __builtin_amdgcn_udot4(l[g1] & (0xFFFFFFFFu >> (8 * (3 - (k1 & 3)))), r[g1], acc, false);
-#endif
     return acc;
 }
 
@@ -468,15 +463,19 @@ static int launch_search(hipStream_t s, StereoExactArgs a, const StereoArgs &f) 
     return MICV_OK;
 }
 
+// Only the forms stereo_exact_covers() admits are instantiated: serial:: with the full window and R <= 5, COLS_2R for R >= 2.
 template <int R, int RPW>
 static int launch_r(hipStream_t s, const StereoExactArgs &a, const StereoArgs &f, bool serial) {
     const int nstrips = cdiv(a.rows, SX_Y);
     stereo_prep_kernel<R><<<dim3(cdiv(a.qhi - a.qlo, 256 - (a.wcols - 1)), nstrips), 256, 0, s>>>(a);
     MICV_LAUNCH_CHECK();
-    const bool full = a.wcols == 2 * R + 1;
-    if (serial) return full ? launch_search<R, 2 * R + 1, SX_SERIAL, RPW>(s, a, f) : MICV_EUNSUPPORTED;
-    if (full) return launch_search<R, 2 * R + 1, SX_SSD, RPW>(s, a, f);
-    return launch_search<R, 2 * R, SX_SSD, RPW>(s, a, f);
+    if constexpr (R <= 5) {
+        if (serial) return launch_search<R, 2 * R + 1, SX_SERIAL, RPW>(s, a, f);
+    }
+    if constexpr (R >= 2) {
+        if (a.wcols == 2 * R) return launch_search<R, 2 * R, SX_SSD, RPW>(s, a, f);
+    }
+    return launch_search<R, 2 * R + 1, SX_SSD, RPW>(s, a, f);
 }
 
 }  // namespace
@@ -492,6 +491,8 @@ bool stereo_exact_covers(int rad, int flags, bool ncc) {
     if (flags & MICV_STEREO_ROLLING) return false;
     if (rad < 1 || rad > 7) return false;                       // (2r+1)^2 * 255^2 < 2^24
     if ((flags & MICV_STEREO_SERIAL) && rad > 5) return false;  // the invalid-position keys need a spare bit
+    // serial:: has the full window and no threshold (stereo_common rejects the combinations; launch_r has no form for them)
+    if ((flags & MICV_STEREO_SERIAL) && (flags & (MICV_STEREO_COLS_2R | MICV_STEREO_MIN_SSD_5E6))) return false;
     if ((flags & MICV_STEREO_COLS_2R) && rad < 2) return false;
     return true;
 }
@@ -548,6 +549,8 @@ size_t stereo_exact_scratch(int rows, int cols, int rad, int min_d, int max_d, i
 int stereo_exact_launch(hipStream_t s, void *scratch, const float *left, const float *right, int rows, int cols,
                         int stride, int rad, int min_d, int max_d, int flags, int wcols, int8_t *disp, int dstride,
                         unsigned *flag, unsigned epoch, int wave_slots3, const StereoArgs &f, bool rows10) {
+    // decided before anything is enqueued: launch_r instantiates exactly the forms this admits
+    if (!stereo_exact_covers(rad, flags, false)) return MICV_EUNSUPPORTED;
     StereoExactArgs a;
     const int nstrips = cdiv(rows, SX_Y);
     a.left = left; a.right = right; a.stride = stride; a.rows = rows; a.cols = cols;

@@ -200,7 +200,10 @@ def test_hand_placed_lds_loads_are_not_touched_before_their_wait():
     load merging costs a v_mov per value there).  hipcc does not count asm loads: a copy, spill or reuse of a
     destination register between the load and the asm `s_waitcnt lgkmcnt(0)` would read stale data, depending
     on timing.  tools/audit_asm_loads.py compiles lk_fused.hip and checks the ISA of every kernel; its
-    detector is checked first on a doctored listing."""
+    detector is checked first on a doctored listing.  The same holds for stereo_exact.hip's asm s_load_dwordx8
+    look-ahead (SGPRs, one column ahead, across the loop's back-edge): its control-flow walk is checked on doctored
+    listings too -- a copy, a spill, a refill, an unwaited branch path, a back-edge, an s_endpgm.  The source must not
+    reintroduce a switch that makes the kernels compute wrong sums on purpose (the removed MICV_SX_NOMASK)."""
     import importlib.util
     import subprocess
     import sys
@@ -222,11 +225,68 @@ def test_hand_placed_lds_loads_are_not_touched_before_their_wait():
         bad = good.replace("\tv_add_u32_e32 v1, v2, v3", bad_line)
         problems, loads, kernels = audit.audit(bad)
         assert len(problems) == 1 and loads == 1, bad_line
+
+    # stereo_exact.hip's scalar look-ahead: one s_load_dwordx8 before the column loop, one per column, retired at the top of
+    # the next column (across the back-edge) and once more behind the loop.  The walk follows the control-flow graph.
+    sgood = """_Zs:
+\ts_mov_b32 s2, 0
+\t;;#ASMSTART
+\ts_load_dwordx8 s[36:43], s[14:15], 0x1c0
+\t;;#ASMEND
+.LBB0_1:                                ; loop header
+\tv_add_u32_e32 v1, v2, v3
+\t;;#ASMSTART
+\ts_waitcnt lgkmcnt(0)
+\t;;#ASMEND
+\ts_and_b32 s18, s39, 0xffffff
+\tv_dot4_u32_u8 v4, s36, v5, v4
+\t;;#ASMSTART
+\ts_load_dwordx8 s[36:43], s[34:35], 0x1e0
+\t;;#ASMEND
+\tds_read_b32 v6, v7
+\ts_add_i32 s2, s2, 1
+\ts_cmp_lt_i32 s2, 4
+\ts_cbranch_scc1 .LBB0_1
+; %bb.2:
+\t;;#ASMSTART
+\ts_waitcnt lgkmcnt(0)
+\t;;#ASMEND
+\ts_endpgm
+"""
+    assert audit.audit_scalar(sgood) == ([], 2, {"_Zs": 2})
+    assert audit.audit(sgood)[0] == []  # no hand-placed LDS load: nothing for the counted-window audit
+    doctored = {
+        "copy": ("\tds_read_b32 v6, v7", "\tds_read_b32 v6, v7\n\ts_mov_b32 s50, s37"),
+        "spill": ("\tds_read_b32 v6, v7", "\tds_read_b32 v6, v7\n\tv_writelane_b32 v200, s38, 4"),
+        "refill": ("\tds_read_b32 v6, v7", "\tds_read_b32 v6, v7\n\tv_readlane_b32 s40, v200, 4"),
+        "branch": ("\ts_add_i32 s2, s2, 1", "\ts_cbranch_execz .LBB0_3\n\ts_add_i32 s2, s2, 1"),
+        # the preheader waits, so only the back-edge reaches the header's use ahead of its wait (a linear scan sees the
+        # use BEFORE the load in the text)
+        "loop": ("\t;;#ASMEND\n.LBB0_1:", "\t;;#ASMEND\n\ts_waitcnt lgkmcnt(0)\n.LBB0_1:"),
+        "endpgm": ("; %bb.2:\n\t;;#ASMSTART\n\ts_waitcnt lgkmcnt(0)\n\t;;#ASMEND\n", "; %bb.2:\n"),
+    }
+    for name, (old, new) in doctored.items():
+        assert old in sgood, name
+        bad = sgood.replace(old, new, 1)
+        if name == "branch":
+            bad += ".LBB0_3:\n\ts_and_b32 s18, s39, 0xff\n\ts_endpgm\n"
+        if name == "loop":
+            bad = bad.replace("\tv_add_u32_e32 v1, v2, v3", "\tv_add_u32_e32 v1, s36, v3")
+        problems, loads, _ = audit.audit_scalar(bad)
+        assert len(problems) == 1 and loads == 2, (name, problems)
+        want = {"copy": "s_mov_b32 s50, s37", "spill": "v_writelane_b32", "refill": "v_readlane_b32",
+                "branch": "s_and_b32 s18, s39, 0xff", "loop": "v_add_u32_e32 v1, s36, v3", "endpgm": "s_endpgm"}[name]
+        assert want in problems[0][2], (name, problems)
+    assert len(audit.REQUIRED_SCALAR) == 2 * (7 + 6 + 5)  # RPW 8 / 10 x (full r 1..7, COLS_2R r 2..7, serial r 1..5)
+    for f in ("introtocomputervision_amd/csrc/stereo_exact.hip", "introtocomputervision_amd/csrc/build.sh", "CMakeLists.txt",
+              "tools/audit_asm_loads.py"):
+        assert "SX_NOMASK" not in open(os.path.join(ROOT, f)).read(), f
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "audit_asm_loads.py")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert ", 0 problems" in r.stdout and " 0 hand-placed" not in r.stdout
+    assert " hand-placed scalar loads in 36 stereo search kernels" in r.stdout, r.stdout[-2000:]
 
 
 def test_shim_functions_have_the_reference_headers_types():
