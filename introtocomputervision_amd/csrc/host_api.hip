@@ -678,6 +678,9 @@ int micv_hough_peaks_host(micv_ctx *ctx, const int32_t *acc, int rows, int cols,
     HOST_PROLOGUE("micv_hough_peaks_host");
     MICV_REQUIRE(acc && count && rows > 0 && cols > 0 && (peaks_rc || num_peaks == 0),
                  "micv_hough_peaks_host: bad argument");
+    MICV_REQUIRE((int64_t)rows * cols < ((int64_t)1 << 31) && num_peaks <= 4096,  // before the upload
+                 "micv_hough_peaks_host: %dx%d accumulator / %u peaks not supported (< 2^31 cells, <= 4096 peaks)",
+                 rows, cols, num_peaks);
     DevBuf da((size_t)rows * cols * 4), dp((size_t)num_peaks * 8 + 8), dn(8);
     MICV_ALLOC_OK(da); MICV_ALLOC_OK(dp); MICV_ALLOC_OK(dn);
     MICV_HIP(hipMemcpyAsync(da.p, acc, (size_t)rows * cols * 4, hipMemcpyHostToDevice, s));

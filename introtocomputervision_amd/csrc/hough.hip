@@ -10,6 +10,7 @@
 //    approximation and not reproducible off NVIDIA parts.
 //  * peaks: up/left 2x2 "local max" flags -> ordered candidate list -> the top num_peaks by
 //    (votes desc, index asc) -- the order thrust::stable_sort(greater) produces (Hough.cu:402).
+#include <algorithm>
 #include <cmath>
 
 #include "compact.hpp"
@@ -551,7 +552,9 @@ int micv_hough_circles_band_dev(micv_ctx *ctx, const uint8_t *mask, int band_row
     MICV_TRY(trig_on_device(ctx, 1, 0, &dt));  // theta = 0..359, Hough.cu:85
     // every accumulator cell is written by its tile (zeros included; the reference forgets to
     // clear, Hough.cu:318)
-    const int reach = (int)std::ceil((double)radius) + 1;
+    // Rows / columns beyond a tile whose points can vote into it.  Capped at rows + cols: a tile's row range and column
+    // filter then already take every point, and radius + 1 would overflow int from radius 2^31 - 1 up.
+    const int reach = (int)std::min<long long>((long long)radius + 1, (long long)rows + cols);
     hough_circles_tiled_kernel<<<dim3(cdiv(cols, 64), cdiv(rows, 32)), 1024, 0, s>>>(
         pts, npts, rows, cols, row0, dt->c, dt->s, (float)radius, reach, acc);
     MICV_LAUNCH_CHECK();

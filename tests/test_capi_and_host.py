@@ -322,3 +322,30 @@ def test_level_kernel_name_needs_no_gpu_and_follows_the_options():
     import ctypes as C
     buf = C.create_string_buffer(160)
     assert _capi.lib.micv_lk_level_kernel_name(None, 15, 1080, 1920, 8, buf, 160) == _capi.EINVAL
+
+
+def test_hough_entry_points_refuse_what_they_cannot_index():
+    """The limits the Hough entry points enforce, checked before the context is used (so no GPU is needed: the
+    context argument only has to be non-null here).  Lines and circles: rows, cols <= 32767 (the circle kernel packs
+    (y, x) into 15 bits each; the line accumulator is then at most 92 680 x 180 cells).  Peaks: fewer than 2^31
+    accumulator cells (32-bit candidate indices) and num_peaks <= 4096.  Bands must lie inside the image."""
+    import ctypes as C
+    from introtocomputervision_amd import _capi, hough
+    lib = _capi.lib
+    fake = C.create_string_buffer(64)  # stands in for the context, the accumulator and the count
+    p = C.addressof(fake)
+    with pytest.raises(_capi.MicvError, match="bad argument"):
+        hough.linesAccumulatorShape(32768, 10)
+    assert hough.linesAccumulatorShape(32767, 32767, 1, 1) == (92680, 180)
+    assert lib.micv_hough_circles_dev(p, p, 10, 32768, 32768, 5, p, None) == _capi.EINVAL
+    assert "bad size 10x32768" in _capi.last_error()
+    assert lib.micv_hough_circles_band_dev(p, p, 10, 20, 20, 95, 100, 5, p, None) == _capi.EINVAL
+    assert "band [95, 105) outside the 100-row image" in _capi.last_error()
+    assert lib.micv_hough_lines_band_dev(p, p, 10, 20, 20, -1, 100, 1, 1, p, None) == _capi.EINVAL
+    assert "outside the 100-row image" in _capi.last_error()
+    assert lib.micv_hough_peaks_dev(p, p, 65536, 32768, 10, 0, p, p, None) == _capi.EINVAL
+    assert "bad size 65536x32768" in _capi.last_error()
+    assert lib.micv_hough_peaks_dev(p, p, 10, 10, 4097, 0, p, p, None) == _capi.EINVAL
+    assert "num_peaks 4097 > 4096" in _capi.last_error()
+    assert lib.micv_hough_peaks_dev(p, p, 10, 10, 5, 0, None, p, None) == _capi.EINVAL
+    assert "peaks_rc is null" in _capi.last_error()
