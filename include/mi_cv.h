@@ -526,6 +526,74 @@ int micv_bf_ratio_filter_host(micv_ctx *ctx, const int32_t *idx2, const float *d
                               double ratio, int32_t *matches_qt, float *distances, int64_t cap,
                               int64_t *count);
 
+/* ------------------------------------------------------------- ps4: RANSAC --------- */
+
+/* ransac::solve, ps4_cpp/lib/RANSAC.cpp:27-152 (called from Solution::ransacHelper,
+ * ps4_cpp/src/Solution.cpp:214-242), with the arithmetic DESIGN.md section 2 fixes.  type is the
+ * reference's TransformType value, which is also the sample size k. */
+#define MICV_RANSAC_TRANSLATION 1
+#define MICV_RANSAC_SIMILARITY  2
+#define MICV_RANSAC_AFFINE      3
+
+/* The reference's sampler (RANSAC.cpp:11-13,20-25,39-40,53): one std::mt19937 seeded once from
+ * std::seed_seq(seed_words, seed_words + nwords) (Config.cpp:85-99; the config default is the one
+ * word 1; seed_words == NULL leaves the engine default-constructed, as before any ransac::seed),
+ * and per solve call a fresh iota index vector that every iteration std::shuffle's in place,
+ * WITHOUT resetting it between iterations; the sample of iteration i is the first k entries
+ * of the vector after i + 1 shuffles.  Host-side, libstdc++'s std::shuffle, no device work.
+ *   samples:     iters x k indices of the next solve over n points; the generator is NOT advanced.
+ *   permutation: the whole index vector after iteration `iter` (0-based) of that solve; not advanced.
+ *   advance:     consumes `iterations` shuffles of n points -- what a solve that ran that many
+ *                iterations consumed -- so the next call sees the next solve's samples. */
+typedef struct micv_ransac_rng micv_ransac_rng;
+int micv_ransac_rng_create(const uint32_t *seed_words, int nwords, micv_ransac_rng **out);
+void micv_ransac_rng_destroy(micv_ransac_rng *rng);
+int micv_ransac_rng_samples(const micv_ransac_rng *rng, int64_t n, int k, int iters, int32_t *samples);
+int micv_ransac_rng_permutation(const micv_ransac_rng *rng, int64_t n, int iter, int32_t *perm);
+int micv_ransac_rng_advance(micv_ransac_rng *rng, int64_t n, int iterations);
+
+/* One solve on the device with the caller's samples (iters x k int32, device; iteration i uses
+ * samples[i*k .. i*k+k-1]).  src_xy / dst_xy: n x {x, y} f32 (device), 1 <= n <= 2^30.
+ * Iteration i scores the hypothesis of its sample against every point whose index is not in the
+ * sample; the run stops after the first i with (double)count_i / (double)n >= min_ratio, or after
+ * iters iterations.  min_ratio <= 0 runs no iteration, as the reference's while loop.
+ * Outputs (device):
+ *   transforms [2][6] f32: [0] the LAST iteration's 2x3 transform -- what the reference returns --
+ *                          [1] the best iteration's (first maximum of count); zeros when none ran;
+ *   inlier_mask [n] u8:    1 where the best iteration counted the point (original indices);
+ *   stats [3] i32:         {iterations, best_iter (-1 when none ran), best_count}.
+ * The reference's consensusSet is the sorted positions, in the best iteration's permutation, of
+ * the points the mask marks (micv_ransac_rng_permutation); its ratio is best_count / n.
+ * A sample index outside [0, n) makes stats = {-1, -1, 0} and every output zero.
+ * Errors (MICV_EINVAL, before anything is enqueued): n < k, a bad type, iters < 1, thresh < 0,
+ * min_ratio NaN, a null pointer. */
+int micv_ransac_solve_dev(micv_ctx *ctx, const float *src_xy, const float *dst_xy, int64_t n,
+                          const int32_t *samples, int iters, int type, int thresh, double min_ratio,
+                          float *transforms, uint8_t *inlier_mask, int32_t *stats, micv_stream stream);
+/* The same with host pointers (the sample indices are checked here): upload, solve, download, sync. */
+int micv_ransac_solve_host(micv_ctx *ctx, const float *src_xy, const float *dst_xy, int64_t n,
+                           const int32_t *samples, int iters, int type, int thresh, double min_ratio,
+                           float *transforms, uint8_t *inlier_mask, int32_t *stats);
+
+/* The device-resident end of the ps4 chain: the points of Solution::ransacHelper
+ * (Solution.cpp:222-225: src = kp_a[queryIdx].xy, dst = kp_b[trainIdx].xy) gathered from the
+ * outputs of micv_sift_keypoints_dev (kp_a [na][4], kp_b [nb][4]) and micv_bf_ratio_filter_dev
+ * (matches_qt [cap][2] and the DEVICE *count, read on the device: n = min(*count, cap)), then the
+ * solve above.  No host round trip.  Since n is not known on the host this form draws its own
+ * samples -- NOT the reference's sequence: for iteration i, draw j = 0 .. k-1, attempt a = 0, 1, ..
+ *     r   = splitmix64(seed ^ ((uint64)i << 32 | (uint64)j << 30 | a))
+ *     idx = ((r >> 32) * n) >> 32                       (64-bit product)
+ * and the first attempt whose idx differs from the sample's earlier entries is entry j.
+ * splitmix64(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *                z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31.
+ * inlier_mask has cap entries (zero at and above n).  n < k on the device gives stats = {0, -1, 0}
+ * and zero outputs; a match index outside kp_a / kp_b gives stats = {-1, -1, 0}. */
+int micv_ransac_solve_matches_dev(micv_ctx *ctx, const float *kp_a, int64_t na, const float *kp_b,
+                                  int64_t nb, const int32_t *matches_qt, const int64_t *count,
+                                  int64_t cap, uint64_t seed, int iters, int type, int thresh,
+                                  double min_ratio, float *transforms, uint8_t *inlier_mask,
+                                  int32_t *stats, micv_stream stream);
+
 /* ----------------------------------- ps7: motion history ----- */
 
 /* mhi::frameDifference, ps7_cpp/lib/MotionHistory.cpp:26-77, for single-channel CV_8U frames:

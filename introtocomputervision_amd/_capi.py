@@ -149,6 +149,16 @@ SIGNATURES = {
     # ps4 matching
     "micv_bf_knn2_dev": (i32, [vp, vp, i32, sz, vp, i32, sz, i32, vp, vp, vp]),
     "micv_bf_ratio_filter_dev": (i32, [vp, vp, vp, i32, f64, vp, vp, i64, vp, vp]),
+    # ps4 RANSAC
+    "micv_ransac_rng_create": (i32, [vp, i32, C.POINTER(vp)]),
+    "micv_ransac_rng_destroy": (None, [vp]),
+    "micv_ransac_rng_samples": (i32, [vp, i64, i32, i32, vp]),
+    "micv_ransac_rng_permutation": (i32, [vp, i64, i32, vp]),
+    "micv_ransac_rng_advance": (i32, [vp, i64, i32]),
+    "micv_ransac_solve_dev": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, f64, vp, vp, vp, vp]),
+    "micv_ransac_solve_host": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, f64, vp, vp, vp]),
+    "micv_ransac_solve_matches_dev": (i32, [vp, vp, i64, vp, i64, vp, vp, i64, C.c_uint64, i32, i32, i32, f64,
+                                            vp, vp, vp, vp]),
     # ps7
     "micv_mhi_frame_difference_dev": (i32, [vp, vp, vp, i32, i32, sz, f64, i32, i32, f64, vp, sz, vp]),
     "micv_mhi_energy_dev": (i32, [vp, vp, i32, i32, sz, vp, sz, vp]),

@@ -751,6 +751,36 @@ int micv_bf_ratio_filter_host(micv_ctx *ctx, const int32_t *idx2, const float *d
     return MICV_OK;
 }
 
+int micv_ransac_solve_host(micv_ctx *ctx, const float *src_xy, const float *dst_xy, int64_t n,
+                           const int32_t *samples, int iters, int type, int thresh, double min_ratio,
+                           float *transforms, uint8_t *inlier_mask, int32_t *stats) {
+    HOST_PROLOGUE("micv_ransac_solve_host");
+    MICV_REQUIRE(src_xy && dst_xy && samples && transforms && inlier_mask && stats,
+                 "micv_ransac_solve_host: null argument");
+    // the argument rules of the device entry point, checked before anything is uploaded
+    MICV_REQUIRE(type >= MICV_RANSAC_TRANSLATION && type <= MICV_RANSAC_AFFINE && iters >= 1 && n >= type &&
+                     n <= (int64_t)1 << 30 && thresh >= 0 && min_ratio == min_ratio,
+                 "micv_ransac_solve_host: bad type %d, iters %d, n = %lld, threshold %d or min_ratio", type, iters,
+                 (long long)n, thresh);
+    const size_t ns = (size_t)iters * type;
+    for (size_t i = 0; i < ns; i++)
+        MICV_REQUIRE(samples[i] >= 0 && samples[i] < n, "micv_ransac_solve_host: sample %lld = %d outside [0, %lld)",
+                     (long long)i, samples[i], (long long)n);
+    DevBuf dsrc((size_t)n * 8), ddst((size_t)n * 8), dsam(ns * 4), dt(48), dm((size_t)n), dst(12);
+    MICV_ALLOC_OK(dsrc); MICV_ALLOC_OK(ddst); MICV_ALLOC_OK(dsam); MICV_ALLOC_OK(dt); MICV_ALLOC_OK(dm);
+    MICV_ALLOC_OK(dst);
+    MICV_HIP(hipMemcpyAsync(dsrc.p, src_xy, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(ddst.p, dst_xy, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(dsam.p, samples, ns * 4, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_ransac_solve_dev(ctx, dsrc.as<float>(), ddst.as<float>(), n, dsam.as<int32_t>(), iters, type,
+                                   thresh, min_ratio, dt.as<float>(), dm.as<uint8_t>(), dst.as<int32_t>(), s));
+    MICV_HIP(hipMemcpyAsync(transforms, dt.p, 48, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipMemcpyAsync(inlier_mask, dm.p, (size_t)n, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipMemcpyAsync(stats, dst.p, 12, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
 int micv_mhi_frame_difference_host(micv_ctx *ctx, const uint8_t *f1, const uint8_t *f2, int rows,
                                    int cols, size_t stride, double thresh, int blur_w, int blur_h,
                                    double blur_sigma, uint8_t *diff, size_t dstride) {

@@ -11,6 +11,7 @@
 #include <map>
 #include <memory>
 #include <ostream>
+#include <random>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -227,6 +228,27 @@ struct Harris {
           gaussian_sigma(n.as<double>("gaussian_sigma")), alpha(n.as<float>("alpha")),
           response_threshold(n.as<double>("response_threshold")), min_distance(n.as<int>("min_distance")) {}
 };
+
+// Config::RANSAC of ps4 (ps4_cpp/lib/Config.cpp:100-104): the ransac_{trans,sim,affine} sections.
+struct RANSAC {
+    int reprojection_threshold = 3;
+    int max_iterations = 2000;
+    double consensus_ratio = 0.75;
+    explicit RANSAC(const Node &n)
+        : reprojection_threshold(n.as<int>("reprojection_threshold")), max_iterations(n.as<int>("max_iterations")),
+          consensus_ratio(n.as<double>("consensus_ratio")) {}
+};
+
+// Config::_mersenneSeed (ps4_cpp/lib/Config.cpp:85-99): the hex words of `mersenne_seed` as a
+// std::seed_seq, or seed_seq({1}) without one.
+inline std::shared_ptr<std::seed_seq> mersenne_seed(const Node &cfg) {
+    if (!cfg.has("mersenne_seed")) return std::shared_ptr<std::seed_seq>(new std::seed_seq({1}));
+    std::istringstream seedString(cfg.as<std::string>("mersenne_seed"));
+    uint32_t i;
+    std::vector<uint32_t> seedVals;
+    while (seedString >> std::hex >> i) seedVals.push_back(i);
+    return std::make_shared<std::seed_seq>(seedVals.begin(), seedVals.end());
+}
 
 // Config::MHI of ps7 (ps7_cpp/lib/Config.cpp:35-47); `last_frame` is in the file but never read there.
 struct MHI {

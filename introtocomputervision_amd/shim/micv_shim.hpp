@@ -6,6 +6,7 @@
 //   pyr::     ProblemSets/ps5_cpp/include/Pyramids.h:7-12
 //   harris::  ProblemSets/ps4_cpp/include/Harris.h:18-96   (cpu:: and gpu:: are the same code here)
 //   sift::    ProblemSets/ps4_cpp/include/Descriptors.h:8-23
+//   ransac::  ProblemSets/ps4_cpp/include/RANSAC.h:10-28
 //   cuda:: / serial::  ps2_cpp/include/DisparitySSD.h:18-43, DisparityNCorr.h:19-44,
 //                      ps1_cpp/src/Hough.h:22-84
 // Inputs are const references and never retained; outputs are (re)allocated by the callee like
@@ -18,7 +19,10 @@
 
 #include <cstring>
 #include <functional>
+#include <memory>
+#include <random>
 #include <stdexcept>
+#include <tuple>
 #include <string>
 #include <utility>
 #include <vector>
@@ -32,6 +36,7 @@
 namespace micv_shim {
 using Mat = cv::Mat;
 using KeyPoint = cv::KeyPoint;
+using Point2f = cv::Point2f;
 using Size = cv::Size;
 // cv::cuda::GpuMat's data pointer must be memory this library's device can address (an OpenCV
 // built against HIP, or unified memory); the overloads below only pass it through.
@@ -50,6 +55,7 @@ inline void create_continuous(GpuMat &m, int rows, int cols, int type) { cv::cud
 namespace micv_shim {
 using Mat = micv::Mat;
 using KeyPoint = micv::KeyPoint;
+using Point2f = micv::Point2f;
 using Size = micv::Size;
 using GpuMat = micv::GpuMat;
 enum { F32 = micv::CV_32F, S8 = micv::CV_8S, U8 = micv::CV_8U, S32 = micv::CV_32S };
@@ -399,6 +405,81 @@ inline void computeDescriptors(const Mat &gradX, const Mat &gradY, const std::ve
     descriptors = out;
 }
 }  // namespace sift
+
+namespace ransac {  // ProblemSets/ps4_cpp/include/RANSAC.h:10-28, RANSAC.cpp:11-152
+using micv_shim::Mat;
+using micv_shim::Point2f;
+enum class TransformType { TRANSLATION = 1, SIMILARITY = 2, AFFINE = 3 };
+namespace detail {
+// The file-static engine and `seeded` flag of RANSAC.cpp:12-13 (one per process).
+inline micv_ransac_rng *&engine() {
+    static micv_ransac_rng *rng = nullptr;
+    if (!rng) micv_shim::check(micv_ransac_rng_create(nullptr, 0, &rng));  // `static std::mt19937 rng;`
+    return rng;
+}
+inline bool &seeded() {
+    static bool s = false;
+    return s;
+}
+}  // namespace detail
+
+// Seeds the engine from the seed sequence's words; every later call is ignored (RANSAC.cpp:20-25).
+inline void seed(std::shared_ptr<std::seed_seq> seq) {
+    if (detail::seeded()) return;
+    std::vector<uint32_t> words(seq->size());
+    seq->param(words.begin());
+    micv_ransac_rng *rng = nullptr;
+    micv_shim::check(micv_ransac_rng_create(words.data(), static_cast<int>(words.size()), &rng));
+    micv_ransac_rng_destroy(detail::engine());
+    detail::engine() = rng;
+    detail::seeded() = true;
+}
+
+// ransac::solve as written: the LAST iteration's transform (an empty Mat when none ran), the best
+// iteration's consensus positions, its ratio; "RANSAC took {} iterations" goes to the kernel-log sink
+// (RANSAC.cpp:148-149).  The reference asserts equal sizes (:34).
+inline std::tuple<Mat, std::vector<int>, double> solve(const std::vector<Point2f> &srcPts,
+                                                       const std::vector<Point2f> &destPts,
+                                                       const TransformType whichTransform,
+                                                       const int ransacReprojThresh = 3, const int maxIters = 2000,
+                                                       const double minConsensusRatio = 0.75) {
+    micv_shim::require(srcPts.size() == destPts.size(), "ransac::solve: point lists of different sizes");
+    const int k = static_cast<int>(whichTransform);
+    const int64_t n = static_cast<int64_t>(srcPts.size());
+    micv_shim::require(n >= k && maxIters >= 1, "ransac::solve: fewer points than the sample, or maxIters < 1");
+    std::vector<float> src(2 * n), dst(2 * n);
+    for (int64_t i = 0; i < n; i++) {
+        src[2 * i] = srcPts[i].x;
+        src[2 * i + 1] = srcPts[i].y;
+        dst[2 * i] = destPts[i].x;
+        dst[2 * i + 1] = destPts[i].y;
+    }
+    micv_ransac_rng *rng = detail::engine();
+    std::vector<int32_t> samples((size_t)maxIters * k);
+    micv_shim::check(micv_ransac_rng_samples(rng, n, k, maxIters, samples.data()));
+    float tr[12];
+    std::vector<uint8_t> mask(n);
+    int32_t stats[3];
+    micv_shim::check(micv_ransac_solve_host(micv_shim::context(), src.data(), dst.data(), n, samples.data(), maxIters,
+                                            k, ransacReprojThresh, minConsensusRatio, tr, mask.data(), stats));
+    std::vector<int> consensusSet;
+    if (stats[2] > 0) {
+        std::vector<int32_t> perm(n);
+        micv_shim::check(micv_ransac_rng_permutation(rng, n, stats[1], perm.data()));
+        for (int64_t p = k; p < n; p++)
+            if (mask[perm[p]]) consensusSet.push_back(static_cast<int>(p));
+    }
+    micv_shim::check(micv_ransac_rng_advance(rng, n, stats[0]));
+    if (micv_shim::kernel_log_sink())
+        micv_shim::kernel_log_sink()("RANSAC took " + std::to_string(stats[0]) + " iterations");
+    Mat transform;
+    if (stats[0] > 0) {
+        transform.create(2, 3, micv_shim::F32);
+        for (int r = 0; r < 2; r++) std::memcpy(transform.ptr<float>(r), tr + 3 * r, 12);
+    }
+    return std::make_tuple(transform, consensusSet, stats[2] > 0 ? double(stats[2]) / double(n) : 0.0);
+}
+}  // namespace ransac
 
 namespace micv_shim {
 inline void disparity(bool ncc, const Mat &left, const Mat &right, const size_t windowRad,
