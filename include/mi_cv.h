@@ -594,6 +594,124 @@ int micv_ransac_solve_matches_dev(micv_ctx *ctx, const float *kp_a, int64_t na, 
                                   double min_ratio, float *transforms, uint8_t *inlier_mask,
                                   int32_t *stats, micv_stream stream);
 
+/* --------------------------------------------------- ps6: particle filter ---------- */
+
+/* ParticleFilter, ps6_cpp/include/ParticleFilter.h and lib/ParticleFilter.cpp, on the device: one tick is
+ * three launches on one stream (score, resample + estimate, model update) with no host sync and no parallel
+ * branch.  The arithmetic is DESIGN.md section 2 ("Particle filter"); in short:
+ *
+ * RNG (cv::RNG, host side, once at create).  state = seed ? seed : 0xffffffff;
+ *   next():  state = (uint64)(uint32)state * 4164903690u + (state >> 32); return (uint32)state;
+ *   uniform(float a, float b) = (float)next() * 2^-32f * (b - a) + a, float arithmetic, unfused;
+ *   gaussian(sigma) = (double)z * sigma with z = randn_0_1_32f, OpenCV 3.4's ziggurat:
+ *     tables (double, then rounded): m1 = 2^31, dn = tn = 3.442619855899, vn = 9.91256303526217e-3,
+ *       q = vn / exp(-.5*dn*dn); kn[0] = (uint32)((dn/q)*m1); kn[1] = 0; wn[0] = (float)(q/m1);
+ *       wn[127] = (float)(dn/m1); fn[0] = 1; fn[127] = (float)exp(-.5*dn*dn);
+ *       for i = 126 .. 1: dn = sqrt(-2*log(vn/dn + exp(-.5*dn*dn))); kn[i+1] = (uint32)((dn/tn)*m1);
+ *                         tn = dn; fn[i] = (float)exp(-.5*dn*dn); wn[i] = (float)(dn/m1);
+ *     draw (NOTE: a word is read from the state BEFORE the state steps, so the first word of a fresh
+ *     generator is its seed's low half):
+ *       loop: hz = (int32)state; step; iz = hz & 127; x = (float)hz * wn[iz];
+ *             if ((uint32)abs(hz) < kn[iz]) return x;                  (abs(INT_MIN) = INT_MIN)
+ *             if (iz == 0) {                                             base strip, r = 3.442620f
+ *               do { x = (float)(uint32)state * 2^-32f; step; y = (float)(uint32)state * 2^-32f; step;
+ *                    x = (float)((double)logf(x + FLT_MIN) * -0.2904764); y = -logf(y + FLT_MIN);
+ *               } while (y + y < x * x);
+ *               return hz > 0 ? r + x : -r - x; }
+ *             y = (float)(uint32)state * 2^-32f; step;
+ *             if ((double)(fn[iz] + y * (fn[iz-1] - fn[iz])) < exp(-.5 * (double)x * (double)x)) return x;
+ *     exp is the library's own double exp (below); logf(v) is (float)log((double)v), log and sqrt the C
+ *     library's (correctly rounded sqrt; the tables are built once).
+ * The RNG quirk of the reference is kept: displaceParticles, resampleMultinomial and genParticles each
+ * construct a fresh cv::RNG, so every tick displaces particle i by the same (gx_i, gy_i) = the i-th pair
+ * of gaussian(sample_sigma) draws of a fresh generator, and resamples with the same n uniform(0, 1)
+ * draws of another fresh generator.  Both tables are made once at create and uploaded once.
+ * Initial particles (genParticles, host, once): a fresh generator; UNIFORM when init == (-1, -1):
+ *   (x, y) = (uniform(0, img_cols), uniform(0, img_rows)); otherwise GAUSSIAN around the model centre
+ *   c = init + (float)size / 2: (x, y) = ((float)(g_x + c.x), (float)(g_y + c.y)) with gaussian(sample_sigma);
+ *   a pair equal (float ==) to an earlier one is drawn again.
+ *
+ * exp(x), double, no contraction (fdlibm's e_exp.c scheme): NaN -> NaN; x > 709.782712893383973096 -> inf;
+ *   x < -745.13321910194110842 -> 0; k = (int)(x * 1.44269504088896338700 + (x < 0 ? -0.5 : 0.5)) (truncation);
+ *   hi = x - k * 6.93147180369123816490e-01; lo = k * 1.90821492927058770002e-10; r = hi - lo; t = r * r;
+ *   c = r - t*(P1 + t*(P2 + t*(P3 + t*(P4 + t*P5)))) with P1..P5 = 1.66666666666666019037e-01,
+ *   -2.77777777770155933842e-03, 6.61375632143793436117e-05, -1.65339022054652515390e-06,
+ *   4.13813679705723846039e-08; y = 1 - ((lo - (r*c)/(2 - c)) - hi); then y * 2^k, as
+ *   (y * 2^1000) * 2^(k-1000) for k > 1000 and (y * 2^(k+1000)) * 2^-1000 for k < -1000.
+ *
+ * One tick (frame: img_rows x img_cols x channels u8, interleaved, `stride` bytes per row):
+ *   displace:  p = ((float)((double)p.x + gx_i), (float)((double)p.y + gy_i));
+ *   weight 0 when p.x < 0 || p.x >= img_cols || p.y < 0 || p.y >= img_rows (float p); otherwise the
+ *   patch's top-left pixel is (cvRound(p.x) - xOff, cvRound(p.y) - yOff) of the frame, xOff = ceil(mcols/2),
+ *   yOff = ceil(mrows/2), cvRound rounds halves to even, coordinates outside clamp (BORDER_REPLICATE);
+ *   MICV_PF_MSE: S = sum over every byte of min(max(m - c, 0)^2, 255) (cv::Mat u8 arithmetic as written:
+ *     the difference and the product saturate), or of (m - c)^2 with MICV_PF_MSE_SIGNED, an exact integer;
+ *     sim = exp(-(S / (double)(mrows*mcols)) / (2 * mse_sigma * mse_sigma));
+ *   MICV_PF_HIST: per channel 32 bins of v >> 3, exact counts; cv::normalize(NORM_L2): h = (float)((double)h
+ *     * (1.0 / sqrt(sum h^2))); chi-square against the model histogram a: sum over bins in order, where
+ *     |a| > DBL_EPSILON, of (double)d * (double)d / a with d = a - h in float; averaged over the channels
+ *     in double, sim = exp(-comp);
+ *   weights: w_i = (float)sim_i; simSum = sum of the double sims in particle order; w_i = (float)(w_i / simSum).
+ *     simSum == 0 or not finite: the displaced particles are kept, w_i = (float)sim_i, and status bit
+ *     MICV_PF_STATUS_NO_WEIGHT is set (the reference divides by zero);
+ *   resample: cum = sequential float prefix sum of w; particle i = old particle upper_bound(cum, u_i),
+ *     the index clamped to n - 1 (MICV_PF_STATUS_CLAMPED; the reference reads one past the end);
+ *   estimate: float mean and variance summed sequentially in particle order, divided by (float)n;
+ *   model update at (cvRound(mean.x), cvRound(mean.y)) (the mean clamped to +-2^24 first; the patch read
+ *     as above): blend = saturate_cast<uchar>((float)alpha * new + (float)(1 - alpha) * old), unfused, with
+ *     cvRound; MICV_PF_MSE blends into the model patch; MICV_PF_HIST always blends from the ORIGINAL model
+ *     patch (the reference never updates _modelPatch there) and the blend's normalized histogram becomes
+ *     the model histogram.
+ * The model is copied at create (the reference's driver keeps a view into frame 0 and paints particles
+ * and the bounding box into it; that is not reproduced). */
+#define MICV_PF_MSE  0 /* ParticleFilter::SimilarityMode::MEAN_SQ_ERR */
+#define MICV_PF_HIST 1 /* ParticleFilter::SimilarityMode::MEAN_SHIFT_LT */
+#define MICV_PF_MSE_SIGNED 1u /* flag: the intended (m - c)^2 instead of the saturating u8 arithmetic */
+#define MICV_PF_STATUS_NO_WEIGHT 1u /* simSum was 0 or not finite: no resampling this tick */
+#define MICV_PF_STATUS_CLAMPED   2u /* some u_i >= cum[n-1]: its index was clamped to n - 1 */
+#define MICV_PF_MAX_PARTICLES 4096
+#define MICV_PF_DEFAULT_SEED 0xffffffffull /* cv::RNG's default state */
+typedef struct micv_pf micv_pf;
+typedef struct micv_pf_state {
+    float x, y, x_var, y_var; /* estimateState(): the particle mean and the x / y variances */
+    uint32_t status;          /* MICV_PF_STATUS_* bits of this tick */
+} micv_pf_state;
+/* model: mrows x mcols x channels u8 (host, mstride bytes per row), copied.  channels 1 or 3;
+ * 1 <= mrows <= img_rows, 1 <= mcols <= img_cols; 1 <= n <= MICV_PF_MAX_PARTICLES; mode MICV_PF_MSE needs
+ * 0 < mse_sigma < inf (MICV_PF_HIST ignores it); sample_sigma finite and >= 0; alpha finite; init_x / init_y
+ * finite ((-1, -1) selects UNIFORM init); flags 0 or MICV_PF_MSE_SIGNED; seed 0 means 0xffffffff as in
+ * cv::RNG.  MICV_EINVAL also when GAUSSIAN init cannot draw n distinct particles in 64 n + 4096 tries.
+ * Synchronous (the tables and the model are uploaded before it returns). */
+int micv_pf_create(micv_ctx *ctx, const uint8_t *model, int mrows, int mcols, size_t mstride, int channels,
+                   int img_rows, int img_cols, int n, int mode, double mse_sigma, double sample_sigma,
+                   float init_x, float init_y, double alpha, uint32_t flags, uint64_t seed, micv_pf **pf);
+void micv_pf_destroy(micv_pf *pf);
+/* One tick on `stream`: frame (device, img_rows x img_cols x channels u8, stride >= img_cols * channels).
+ * The state goes to state_dev (device, may be NULL) and stays readable through the calls below.
+ * Asynchronous; MICV_EINVAL (nothing enqueued) for a null pf / frame or a bad stride. */
+int micv_pf_tick_dev(micv_pf *pf, const uint8_t *frame, size_t stride, micv_stream stream,
+                     micv_pf_state *state_dev);
+/* The same from a host frame: upload, tick, download of the state, sync. */
+int micv_pf_tick_host(micv_pf *pf, const uint8_t *frame, size_t stride, micv_pf_state *state);
+/* The current particles (n x {x, y} f32) and weights (n f32: the normalized weights of the last tick,
+ * before resampling, as the reference's _weights; 1/n before the first tick).  _dev copies on `stream`
+ * into device memory, _host copies out and syncs.  The _host calls (and micv_pf_tick_host) run on the null
+ * stream: after a micv_pf_tick_dev on a non-blocking stream, synchronise that stream first. */
+int micv_pf_particles_dev(micv_pf *pf, float *xy, micv_stream stream);
+int micv_pf_particles_host(micv_pf *pf, float *xy);
+int micv_pf_weights_dev(micv_pf *pf, float *w, micv_stream stream);
+int micv_pf_weights_host(micv_pf *pf, float *w);
+/* The model: patch (mrows x mcols x channels u8, dense; MICV_PF_MSE: the current model patch, MICV_PF_HIST:
+ * the last blend, the original model before the first tick) and hist (channels x 32 f32, MICV_PF_HIST's
+ * model histogram, zeros in MICV_PF_MSE).  Either may be NULL.  Syncs. */
+int micv_pf_model_host(micv_pf *pf, uint8_t *patch, float *hist);
+/* nframes ticks over host frames (each img_rows x img_cols x channels u8, `stride` bytes per row): every
+ * frame uploaded once, the upload of frame t + 1 beside tick t.  states: nframes entries; particles (may be
+ * NULL): nframes x n x {x, y} f32, the particles after each tick.  Byte-identical to nframes calls of
+ * micv_pf_tick_host (and micv_pf_particles_host).  Blocking. */
+int micv_pf_track_seq_host(micv_pf *pf, const uint8_t *const *frames, int nframes, size_t stride,
+                           micv_pf_state *states, float *particles);
+
 /* ----------------------------------- ps7: motion history ----- */
 
 /* mhi::frameDifference, ps7_cpp/lib/MotionHistory.cpp:26-77, for single-channel CV_8U frames:

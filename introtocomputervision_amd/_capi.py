@@ -159,6 +159,18 @@ SIGNATURES = {
     "micv_ransac_solve_host": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, f64, vp, vp, vp]),
     "micv_ransac_solve_matches_dev": (i32, [vp, vp, i64, vp, i64, vp, vp, i64, C.c_uint64, i32, i32, i32, f64,
                                             vp, vp, vp, vp]),
+    # ps6 particle filter
+    "micv_pf_create": (i32, [vp, vp, i32, i32, sz, i32, i32, i32, i32, i32, f64, f64, f32, f32, f64, u32,
+                             C.c_uint64, C.POINTER(vp)]),
+    "micv_pf_destroy": (None, [vp]),
+    "micv_pf_tick_dev": (i32, [vp, vp, sz, vp, vp]),
+    "micv_pf_tick_host": (i32, [vp, vp, sz, vp]),
+    "micv_pf_particles_dev": (i32, [vp, vp, vp]),
+    "micv_pf_particles_host": (i32, [vp, vp]),
+    "micv_pf_weights_dev": (i32, [vp, vp, vp]),
+    "micv_pf_weights_host": (i32, [vp, vp]),
+    "micv_pf_model_host": (i32, [vp, vp, vp]),
+    "micv_pf_track_seq_host": (i32, [vp, vp, i32, sz, vp, vp]),
     # ps7
     "micv_mhi_frame_difference_dev": (i32, [vp, vp, vp, i32, i32, sz, f64, i32, i32, f64, vp, sz, vp]),
     "micv_mhi_energy_dev": (i32, [vp, vp, i32, i32, sz, vp, sz, vp]),

@@ -253,3 +253,26 @@ def hough_circle_params(cfg, section):
     """Config::HoughCircle (ps1): min_radius, max_radius, num_peaks, threshold."""
     n = cfg.child(section)
     return {k: n.as_int(k) for k in ("min_radius", "max_radius", "num_peaks", "threshold")}
+
+
+def pf_params(cfg, section):
+    """Config::PFConf of ps6 (ps6_cpp/lib/Config.cpp:105-115): a pfconf* section."""
+    n = cfg[section]
+    return dict(num_particles=int(n["num_particles"]), mse_sigma=float(n["mse_sigma"]),
+                dynamics_sigma=float(n["dynamics_sigma"]), alpha=float(n["alpha"]))
+
+
+def load_bbox(path):
+    """Config::Tracking::loadBBox of ps6 (ps6_cpp/lib/Config.cpp:51-103) -> ((x, y), (width, height)) as floats:
+    two lines of two space-separated numbers."""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    if len(lines) < 2:
+        raise ConfigError(f"{path}: expected two lines")
+    out = []
+    for ln in lines[:2]:
+        vals = [float(t) for t in ln.split()]
+        if len(vals) != 2:
+            raise ConfigError(f"{path}: expected 2 values on each line")
+        out.append(tuple(vals))
+    return out[0], out[1]

@@ -250,6 +250,43 @@ inline std::shared_ptr<std::seed_seq> mersenne_seed(const Node &cfg) {
     return std::make_shared<std::seed_seq>(seedVals.begin(), seedVals.end());
 }
 
+// Config::PFConf of ps6 (ps6_cpp/lib/Config.cpp:105-115): the pfconf* sections.
+struct PFConf {
+    double mse_sigma = 0, dynamics_sigma = 0, alpha = 0;
+    size_t num_particles = 0;
+    explicit PFConf(const Node &n)
+        : mse_sigma(n.as<double>("mse_sigma")), dynamics_sigma(n.as<double>("dynamics_sigma")),
+          alpha(n.as<double>("alpha")), num_particles(n.as<size_t>("num_particles")) {}
+};
+
+// Config::Tracking::loadBBox of ps6 (ps6_cpp/lib/Config.cpp:51-103): line 1 the (x, y) of the bounding box's
+// top-left corner, line 2 its width and height, two space-separated floats each.  False on a bad file.
+struct BBox {
+    float x = 0, y = 0, width = 0, height = 0;
+};
+inline bool load_bbox(const std::string &filename, BBox &out) {
+    std::ifstream input(filename);
+    if (!input.is_open()) return false;
+    float v[2][2];
+    for (int l = 0; l < 2; l++) {
+        std::string line;
+        if (!std::getline(input, line)) return false;
+        std::istringstream tokens(line);
+        std::vector<float> vals;
+        std::string tok;
+        while (tokens >> tok) {
+            char *end = nullptr;
+            const float f = std::strtof(tok.c_str(), &end);
+            if (end == tok.c_str() || *end) return false;
+            vals.push_back(f);
+        }
+        if (vals.size() != 2) return false;
+        v[l][0] = vals[0], v[l][1] = vals[1];
+    }
+    out.x = v[0][0], out.y = v[0][1], out.width = v[1][0], out.height = v[1][1];
+    return true;
+}
+
 // Config::MHI of ps7 (ps7_cpp/lib/Config.cpp:35-47); `last_frame` is in the file but never read there.
 struct MHI {
     double diff_threshold = 0;

@@ -156,6 +156,12 @@ private:
 
 struct Point2f {
     float x = 0, y = 0;
+    Point2f() = default;
+    Point2f(float x_, float y_) : x(x_), y(y_) {}
+};
+struct Scalar {  // cv::Scalar: four doubles, B, G, R, A for a colour
+    double val[4];
+    Scalar(double v0 = 0, double v1 = 0, double v2 = 0, double v3 = 0) : val{v0, v1, v2, v3} {}
 };
 struct KeyPoint {  // cv::KeyPoint(x, y, size, angle, response)
     Point2f pt;

@@ -7,6 +7,7 @@
 //   harris::  ProblemSets/ps4_cpp/include/Harris.h:18-96   (cpu:: and gpu:: are the same code here)
 //   sift::    ProblemSets/ps4_cpp/include/Descriptors.h:8-23
 //   ransac::  ProblemSets/ps4_cpp/include/RANSAC.h:10-28
+//   ParticleFilter  ProblemSets/ps6_cpp/include/ParticleFilter.h (the class, in the global namespace)
 //   cuda:: / serial::  ps2_cpp/include/DisparitySSD.h:18-43, DisparityNCorr.h:19-44,
 //                      ps1_cpp/src/Hough.h:22-84
 // Inputs are const references and never retained; outputs are (re)allocated by the callee like
@@ -17,8 +18,10 @@
 // take the minimal micv::Mat of micv_mat.hpp (this image has no OpenCV).
 #pragma once
 
+#include <cmath>
 #include <cstring>
 #include <functional>
+#include <iostream>
 #include <memory>
 #include <random>
 #include <stdexcept>
@@ -33,11 +36,13 @@
 #include <opencv2/core/core.hpp>
 #include <opencv2/core/cuda.hpp>
 #include <opencv2/core/types.hpp>
+#include <opencv2/imgproc/imgproc.hpp>
 namespace micv_shim {
 using Mat = cv::Mat;
 using KeyPoint = cv::KeyPoint;
 using Point2f = cv::Point2f;
 using Size = cv::Size;
+using Scalar = cv::Scalar;
 // cv::cuda::GpuMat's data pointer must be memory this library's device can address (an OpenCV
 // built against HIP, or unified memory); the overloads below only pass it through.
 using GpuMat = cv::cuda::GpuMat;
@@ -57,6 +62,7 @@ using Mat = micv::Mat;
 using KeyPoint = micv::KeyPoint;
 using Point2f = micv::Point2f;
 using Size = micv::Size;
+using Scalar = micv::Scalar;
 using GpuMat = micv::GpuMat;
 enum { F32 = micv::CV_32F, S8 = micv::CV_8S, U8 = micv::CV_8U, S32 = micv::CV_32S };
 inline micv_ctx *context() { return micv::thread_context(); }
@@ -480,6 +486,90 @@ inline std::tuple<Mat, std::vector<int>, double> solve(const std::vector<Point2f
     return std::make_tuple(transform, consensusSet, stats[2] > 0 ? double(stats[2]) / double(n) : 0.0);
 }
 }  // namespace ransac
+
+// ParticleFilter, ProblemSets/ps6_cpp/include/ParticleFilter.h and lib/ParticleFilter.cpp, on micv_pf_* (the
+// arithmetic of mi_cv.h's "ps6: particle filter" block).  The model (8-bit, 1 or 3 channels) is copied: the
+// reference keeps a view into the caller's frame, into which its driver then paints.  Errors throw
+// std::runtime_error (the reference asserts or divides by zero).
+class ParticleFilter {
+public:
+    enum class SimilarityMode { MEAN_SQ_ERR, MEAN_SHIFT_LT };
+    ParticleFilter(const micv_shim::Mat &model,
+                   const micv_shim::Size &imSize,
+                   const size_t numParticles,
+                   const SimilarityMode simMode,
+                   const double mseSigma,
+                   const double sampleSigma,
+                   const micv_shim::Point2f &initModelPos = micv_shim::Point2f(-1, -1),
+                   const double alpha = 0.1)
+        : _imSize(imSize), _numParticles(numParticles) {
+        micv_shim::require(model.depth() == micv_shim::U8 && (model.channels() == 1 || model.channels() == 3),
+                           "ParticleFilter: the model must be 8-bit with 1 or 3 channels");
+        micv_shim::require(numParticles >= 1 && numParticles <= MICV_PF_MAX_PARTICLES,
+                           "ParticleFilter: numParticles outside 1 .. MICV_PF_MAX_PARTICLES");
+        micv_pf *pf = nullptr;
+        micv_shim::check(micv_pf_create(micv_shim::context(), model.data, model.rows, model.cols,
+                                        static_cast<size_t>(model.step), model.channels(), imSize.height, imSize.width,
+                                        static_cast<int>(numParticles), static_cast<int>(simMode), mseSigma,
+                                        sampleSigma, initModelPos.x, initModelPos.y, alpha, 0, MICV_PF_DEFAULT_SEED,
+                                        &pf));
+        _pf = std::shared_ptr<micv_pf>(pf, micv_pf_destroy);
+        _channels = model.channels();
+        std::cout << "Initialized" << std::endl;  // ParticleFilter.cpp:29
+        fetchParticles();
+    }
+
+    // Update the particle filter with a new frame: {(x, y) mean of the particles, x variance, y variance}
+    std::tuple<micv_shim::Point2f, float, float> tick(const micv_shim::Mat &frame) {
+        micv_shim::require(frame.depth() == micv_shim::U8 && frame.channels() == _channels &&
+                               frame.rows == _imSize.height && frame.cols == _imSize.width,
+                           "ParticleFilter::tick: the frame's size or type differs from the filter's");
+        micv_pf_state st;
+        micv_shim::check(micv_pf_tick_host(_pf.get(), frame.data, static_cast<size_t>(frame.step), &st));
+        fetchParticles();
+        return std::make_tuple(micv_shim::Point2f(st.x, st.y), st.x_var, st.y_var);
+    }
+
+    const std::vector<micv_shim::Point2f> &getParticles() const { return _particles; }
+
+    // cv::circle(img, p, 1, color, -1) per particle (ParticleFilter.cpp:82-86).  Without OpenCV: the pixels within
+    // distance 1 of cvRound(p), the centre and its four neighbours (parity with OpenCV's rasteriser unpinned).
+    void drawParticles(micv_shim::Mat &img, const micv_shim::Scalar &color) {
+#ifdef MICV_SHIM_WITH_OPENCV
+        for (const auto &p : _particles) cv::circle(img, p, 1, color, -1);
+#else
+        micv_shim::require(img.depth() == micv_shim::U8, "ParticleFilter::drawParticles: 8-bit images only");
+        const int cn = img.channels() < 4 ? img.channels() : 4;
+        for (const auto &p : _particles) {
+            if (!(p.x > -2.f && p.x < img.cols + 2.f && p.y > -2.f && p.y < img.rows + 2.f)) continue;
+            const int cx = static_cast<int>(std::nearbyint(p.x)), cy = static_cast<int>(std::nearbyint(p.y));
+            const int off[5][2] = {{0, 0}, {-1, 0}, {1, 0}, {0, -1}, {0, 1}};
+            for (const auto &o : off) {
+                const int x = cx + o[0], y = cy + o[1];
+                if (x < 0 || y < 0 || x >= img.cols || y >= img.rows) continue;
+                unsigned char *d = img.ptr<unsigned char>(y) + static_cast<size_t>(x) * img.channels();
+                for (int k = 0; k < cn; k++) {
+                    const double v = std::nearbyint(color.val[k]);
+                    d[k] = static_cast<unsigned char>(v < 0 ? 0 : (v > 255 ? 255 : v));
+                }
+            }
+        }
+#endif
+    }
+
+private:
+    void fetchParticles() {
+        std::vector<float> xy(2 * _numParticles);
+        micv_shim::check(micv_pf_particles_host(_pf.get(), xy.data()));
+        _particles.resize(xy.size() / 2);
+        for (size_t i = 0; i < _particles.size(); i++) _particles[i] = micv_shim::Point2f(xy[2 * i], xy[2 * i + 1]);
+    }
+    std::shared_ptr<micv_pf> _pf;
+    const micv_shim::Size _imSize;
+    const size_t _numParticles;
+    int _channels = 0;
+    std::vector<micv_shim::Point2f> _particles;
+};
 
 namespace micv_shim {
 inline void disparity(bool ncc, const Mat &left, const Mat &right, const size_t windowRad,
