@@ -743,6 +743,111 @@ int micv_mhi_update_dev(micv_ctx *ctx, uint8_t *history, size_t hstride, const u
 int micv_mhi_update_host(micv_ctx *ctx, uint8_t *history, size_t hstride, const uint8_t *mask,
                          size_t mstride, int rows, int cols, int tau);
 
+/* MHI sequence: mhiHelper's loop (ps7_cpp/src/Solution.cpp:16-101) over F frames of one video.  Frame f (0-based) is
+ * at frames + f * frame_pitch, rows of `stride` bytes.  The history starts at zero; update number j (j = 1..F-1) is
+ * frameDifference(frame j-1, frame j) then calcMotionHistory, and save[i] = j stores the history after update j into
+ * out + i * out_pitch (rows of out_stride bytes): mhiHelper's frameNum.  A save number outside 1..F-1 is MICV_EINVAL.
+ * The history and difference planes live in the context scratch beside frameDifference's own. */
+int micv_mhi_history_seq_dev(micv_ctx *ctx, const uint8_t *frames, int nframes, size_t frame_pitch, size_t stride,
+                             int rows, int cols, double thresh, int blur_w, int blur_h, double blur_sigma, int tau,
+                             const int *save, int nsave, uint8_t *out, size_t out_pitch, size_t out_stride,
+                             micv_stream stream);
+/* Uploads every frame once, runs the _dev form on the null stream, downloads the saved histories. */
+int micv_mhi_history_seq_host(micv_ctx *ctx, const uint8_t *frames, int nframes, size_t frame_pitch, size_t stride,
+                              int rows, int cols, double thresh, int blur_w, int blur_h, double blur_sigma, int tau,
+                              const int *save, int nsave, uint8_t *out, size_t out_pitch, size_t out_stride);
+
+/* ------------------------------------------------------- ps7: central moments ------- */
+
+/* moments::centralMoment (ps7_cpp/lib/Moments.cpp) for `batch` single-channel images: image b starts at
+ * imgs + b * img_pitch bytes, rows of `stride` bytes, `type` MICV_MOMENTS_U8 or MICV_MOMENTS_F32.  `orders` (host) holds
+ * n pairs (p, q), p, q >= 0, p + q <= MICV_MOMENTS_MAX_ORDER, n <= MICV_MOMENTS_MAX_ORDERS.  Out (f32): mu[batch][n],
+ * eta[batch][n] and, when raw is not NULL, raw[batch][3] = M00, M10, M01.  Stream-ordered, no host sync; bad arguments
+ * return MICV_EINVAL before anything is enqueued.  Images above 2^24 pixels are MICV_EINVAL (the exact sums' int64
+ * headroom: a term is below 2^39 in its bin).
+ *
+ * Arithmetic contract (each step as Moments.cpp and the driver write it):
+ *   v     u8 -> (float)v (convertTo CV_32FC1, :14); f32 as given.  MICV_MOMENTS_NORM_INF (u8 only) first applies
+ *         cv::normalize(mhi, mhi, 1.0, 0.0, NORM_INF, CV_32FC1) (Solution.cpp:243-245): v = fl((float)u * s) with
+ *         s = (float)(1.0 / max) computed in double, s = 0 when the image max is 0 (OpenCV 3's normalize -> convertTo
+ *         with a float work type).
+ *   x, y  column and row as f32 (the iota matrices, :17-39).  M00 = S v, M10 = S fl(x v), M01 = S fl(y v) (:45-47);
+ *         xBar = fl(M10 / M00), yBar = fl(M01 / M00), f32, correctly rounded (:49-50).
+ *   dx    fl(x - xBar).  dy = fl(x - yBar) AS WRITTEN (:59 is cv::pow(xFull - yBar, q, yPow)); MICV_MOMENTS_Y_FIXED
+ *         uses fl(y - yBar).
+ *   pow   cv::pow with an integer power on f32: power 0 -> 1.0f (even for NaN), 1 -> copy, otherwise iPow_'s loop
+ *         a = 1, b = d; while (p > 1) { if (p & 1) a *= b; b *= b; p >>= 1; } a *= b, in f32.
+ *   term  fl(dy^q * fl(dx^p * v)) (yPow.mul(xPow.mul(fltImg)), :61).
+ *   S     every sum is the exact sum of its f32 terms, rounded once to double (RNE), then to f32
+ *         (float M = cv::sum(...)[0]).  OpenCV's own order -- a serial double chain over float partials of four, SIMD
+ *         dependent -- cannot be reproduced by a parallel reduction; exact-then-round is the order-independent limit
+ *         of all such orders (tests/test_ps7_ref.py bounds the difference on a 480 x 640 MHI: <= 4 f32 ulp).
+ *   eta   (float)((double)mu / P), P = pow(M00, 1 + (p+q)/2) from IEEE basic operations only: d = (double)M00,
+ *         P = d * d * ... * d (the integer part of the power, left to right), times sqrt(d) (correctly rounded) when
+ *         p + q is odd.  P is within 3 ulp of glibc pow over the sweep tests/test_ps7_ref.py runs (M00 in
+ *         [1e-3, 1e7], powers 1 .. 5); host, device and the tests agree bit for bit.
+ *   non-finite  M00 = 0 gives NaN centroids and whatever the steps make of them; a NaN term, or +Inf with -Inf, makes
+ *         a sum NaN, otherwise +-Inf terms make it +-Inf.  Output NaNs are the canonical quiet NaN 0x7FC00000. */
+#define MICV_MOMENTS_U8 0
+#define MICV_MOMENTS_F32 1
+#define MICV_MOMENTS_NORM_INF 1u
+#define MICV_MOMENTS_Y_FIXED 2u
+#define MICV_MOMENTS_MAX_ORDERS 16
+#define MICV_MOMENTS_MAX_ORDER 8
+int micv_central_moments_dev(micv_ctx *ctx, const void *imgs, int batch, size_t img_pitch, size_t stride, int rows,
+                             int cols, int type, const int *orders, int n, uint32_t flags, float *mu, float *eta,
+                             float *raw, micv_stream stream);
+int micv_central_moments_host(micv_ctx *ctx, const void *imgs, int batch, size_t img_pitch, size_t stride, int rows,
+                              int cols, int type, const int *orders, int n, uint32_t flags, float *mu, float *eta,
+                              float *raw);
+
+/* ----------------------------------------- ps7: k-NN and confusion matrices --------- */
+
+/* cv::ml::KNearest::train(ROW_SAMPLE) + findNearest(test, k, results), brute force, classifier mode.  train is
+ * ntrain x dims f32 (row stride in bytes), labels int32; test is ntest x dims.  pred[ntest] int32.  dims <= 64,
+ * k <= 32, row counts below 2^24.  One lane per test row.
+ *
+ * The contract, written from OpenCV 3.4's knearest.cpp as recalled: UNPINNED (OpenCV is not available to check it,
+ * as DESIGN.md section 3 says of the other OpenCV-carried arithmetic).
+ *   distance  f32 s = 0; per group of four dims t_i = fl(u_i - v_i), s = fl(s + (((t0*t0 + t1*t1) + t2*t2) + t3*t3))
+ *             without FMA; then the remaining dims one at a time, s = fl(s + t*t); the distance is (float)s.
+ *             MICV_KNN_F64_ACC: double s and double t_i = (double)fl(u_i - v_i) (OpenCV 2.4's CvKNearest form).
+ *   insertion k = min(k, train rows); k slots start at FLT_MAX with response 0; a candidate goes after every slot whose
+ *             distance bits (int32) are <= its own, so equal distances keep the earlier train row; +Inf and NaN (any
+ *             sign bit) compare above FLT_MAX and are never inserted.
+ *   vote      bubble-sort the k responses ascending and take the longest run; on a tie the first (smallest) label
+ *             wins.  Empty slots vote 0. */
+#define MICV_KNN_F64_ACC 1u
+#define MICV_KNN_MAX_DIMS 64
+#define MICV_KNN_MAX_K 32
+#define MICV_KNN_MAX_LABELS 16
+#define MICV_KNN_MAX_GROUPS 32
+int micv_knn_predict_dev(micv_ctx *ctx, const float *train, int ntrain, size_t train_stride, const int *train_labels,
+                         const float *test, int ntest, size_t test_stride, int dims, int k, uint32_t flags, int *pred,
+                         micv_stream stream);
+int micv_knn_predict_host(micv_ctx *ctx, const float *train, int ntrain, size_t train_stride, const int *train_labels,
+                          const float *test, int ntest, size_t test_stride, int dims, int k, uint32_t flags, int *pred);
+/* matching::naiveConfusionMatrix (groups NULL) and matching::confusionMatrix (Matching.cpp) over n rows of features
+ * with labels in 1..num_labels (L <= 16).
+ *   groups NULL  leave-one-out: each row is tested against all others in their original order; confusion holds one
+ *                L x L matrix.
+ *   groups       for g = 1..num_groups (G <= 32) the train set is the rows with group != g in original order, the test
+ *                set the rows with group == g; confusion holds G matrices and then their average ((G + 1) x L x L).  A
+ *                row whose group is outside 1..G is in no fold (prediction 0) but is trained on in every fold.
+ * pred[n] (may be NULL) receives each tested row's vote in its own fold.  A row whose label or vote is outside 1..L is
+ * left out of the matrices and counted in *left_out (may be NULL); the reference asserts there, the library does not.
+ * Matrices: confusion[expected-1][result-1] += 1 and counts[expected-1] += 1 in f32; each row divided by its count as
+ * OpenCV 3's divide does (0 where the count is 0); the average is fl(fl(fl(0 + C1) + C2) + ...) * (float)(1.0 / G)
+ * (avg / float(n) is a MatExpr evaluated as convertTo(alpha = 1/n), not a division).
+ * Not restated: arrangeTrainingData's BOTH mode (Solution.cpp:166-182) indexes past the moment vector -- undefined
+ * behaviour the driver never reaches. */
+int micv_knn_confusion_dev(micv_ctx *ctx, const float *features, int n, size_t stride, int dims, const int *labels,
+                           const int *groups, int num_labels, int num_groups, int k, uint32_t flags, float *confusion,
+                           int *pred, int *left_out, micv_stream stream);
+int micv_knn_confusion_host(micv_ctx *ctx, const float *features, int n, size_t stride, int dims, const int *labels,
+                            const int *groups, int num_labels, int num_groups, int k, uint32_t flags, float *confusion,
+                            int *pred, int *left_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,12 @@ f64 = C.c_double
 
 OK, EINVAL, EHIP, ENOMEM, EUNSUPPORTED = 0, -1, -2, -3, -4
 STEREO_COLS_2R, STEREO_MIN_SSD_5E6, STEREO_SERIAL, STEREO_ROLLING = 1, 2, 4, 8
+# ps7 (mi_cv.h): central moments and k-NN
+MOMENTS_U8, MOMENTS_F32 = 0, 1
+MOMENTS_NORM_INF, MOMENTS_Y_FIXED = 1, 2
+MOMENTS_MAX_ORDERS, MOMENTS_MAX_ORDER = 16, 8
+KNN_F64_ACC = 1
+KNN_MAX_DIMS, KNN_MAX_K, KNN_MAX_LABELS, KNN_MAX_GROUPS = 64, 32, 16, 32
 # micv_ctx_set_option (include/mi_cv.h): none of these changes a result
 (OPT_LK_STREAM_GROUPS, OPT_LK_FORCE_GENERIC, OPT_LK_NARROW_TILES, OPT_SOBEL_GENERIC, OPT_HARRIS_GENERIC,
  OPT_NMS_SCAN, OPT_STEREO_ROWS, OPT_LK_CHAIN, OPT_LK_SHORT_TILES, OPT_LK_STREAM, OPT_LK_TALL_TILES,
@@ -184,6 +190,15 @@ SIGNATURES = {
     "micv_mhi_frame_difference_host": (i32, [vp, vp, vp, i32, i32, sz, f64, i32, i32, f64, vp, sz]),
     "micv_mhi_threshold_host": (i32, [vp, vp, i32, i32, sz, f64, vp, sz]),
     "micv_mhi_update_host": (i32, [vp, vp, sz, vp, sz, i32, i32, i32]),
+    "micv_mhi_history_seq_dev": (i32, [vp, vp, i32, sz, sz, i32, i32, f64, i32, i32, f64, i32, vp, i32, vp, sz, sz,
+                                       vp]),
+    "micv_mhi_history_seq_host": (i32, [vp, vp, i32, sz, sz, i32, i32, f64, i32, i32, f64, i32, vp, i32, vp, sz, sz]),
+    "micv_central_moments_dev": (i32, [vp, vp, i32, sz, sz, i32, i32, i32, vp, i32, u32, vp, vp, vp, vp]),
+    "micv_central_moments_host": (i32, [vp, vp, i32, sz, sz, i32, i32, i32, vp, i32, u32, vp, vp, vp]),
+    "micv_knn_predict_dev": (i32, [vp, vp, i32, sz, vp, vp, i32, sz, i32, i32, u32, vp, vp]),
+    "micv_knn_predict_host": (i32, [vp, vp, i32, sz, vp, vp, i32, sz, i32, i32, u32, vp]),
+    "micv_knn_confusion_dev": (i32, [vp, vp, i32, sz, i32, vp, vp, i32, i32, i32, u32, vp, vp, vp, vp]),
+    "micv_knn_confusion_host": (i32, [vp, vp, i32, sz, i32, vp, vp, i32, i32, i32, u32, vp, vp, vp]),
 }
 
 MISSING = []

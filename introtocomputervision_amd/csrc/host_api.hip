@@ -845,4 +845,99 @@ int micv_mhi_update_host(micv_ctx *ctx, uint8_t *history, size_t hstride, const 
     return MICV_OK;
 }
 
+
+int micv_mhi_history_seq_host(micv_ctx *ctx, const uint8_t *frames, int nframes, size_t frame_pitch, size_t stride,
+                              int rows, int cols, double thresh, int blur_w, int blur_h, double blur_sigma, int tau,
+                              const int *save, int nsave, uint8_t *out, size_t out_pitch, size_t out_stride) {
+    HOST_PROLOGUE("micv_mhi_history_seq_host");
+    MICV_REQUIRE(frames && save && out && nframes >= 2 && nsave >= 1 && rows > 0 && cols > 0 &&
+                     stride >= (size_t)cols && frame_pitch >= stride * (size_t)rows && out_stride >= (size_t)cols &&
+                     (nsave == 1 || out_pitch >= out_stride * (size_t)rows),
+                 "micv_mhi_history_seq_host: bad argument");
+    const size_t n = (size_t)rows * cols;
+    DevBuf df(n * nframes), dout(n * nsave);
+    MICV_ALLOC_OK(df); MICV_ALLOC_OK(dout);
+    for (int f = 0; f < nframes; f++)
+        MICV_TRY(up2d(df.as<uint8_t>() + n * f, frames + (size_t)f * frame_pitch, stride, (size_t)cols, rows, s));
+    MICV_TRY(micv_mhi_history_seq_dev(ctx, df.as<uint8_t>(), nframes, n, cols, rows, cols, thresh, blur_w, blur_h,
+                                      blur_sigma, tau, save, nsave, dout.as<uint8_t>(), n, cols, s));
+    for (int i = 0; i < nsave; i++)
+        MICV_TRY(down2d(out + (size_t)i * out_pitch, out_stride, dout.as<uint8_t>() + n * i, (size_t)cols, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_central_moments_host(micv_ctx *ctx, const void *imgs, int batch, size_t img_pitch, size_t stride, int rows,
+                              int cols, int type, const int *orders, int n, uint32_t flags, float *mu, float *eta,
+                              float *raw) {
+    HOST_PROLOGUE("micv_central_moments_host");
+    MICV_REQUIRE(imgs && orders && mu && eta && batch > 0 && rows > 0 && cols > 0 && n >= 1 &&
+                     n <= MICV_MOMENTS_MAX_ORDERS && (type == MICV_MOMENTS_U8 || type == MICV_MOMENTS_F32),
+                 "micv_central_moments_host: bad argument");
+    const size_t elem = type == MICV_MOMENTS_F32 ? 4 : 1, row_bytes = (size_t)cols * elem;
+    MICV_REQUIRE(stride >= row_bytes && (batch == 1 || img_pitch >= stride * (size_t)rows),
+                 "micv_central_moments_host: bad stride / pitch");
+    const size_t img = row_bytes * rows;
+    DevBuf di(img * batch), dout(sizeof(float) * (size_t)batch * (2 * n + 3));
+    MICV_ALLOC_OK(di); MICV_ALLOC_OK(dout);
+    for (int b = 0; b < batch; b++)
+        MICV_TRY(up2d(di.as<uint8_t>() + img * b, static_cast<const uint8_t *>(imgs) + (size_t)b * img_pitch, stride,
+                      row_bytes, rows, s));
+    float *dmu = dout.as<float>(), *deta = dmu + (size_t)batch * n, *draw = deta + (size_t)batch * n;
+    MICV_TRY(micv_central_moments_dev(ctx, di.p, batch, img, row_bytes, rows, cols, type, orders, n, flags, dmu, deta,
+                                      draw, s));
+    MICV_HIP(hipMemcpyAsync(mu, dmu, sizeof(float) * batch * n, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipMemcpyAsync(eta, deta, sizeof(float) * batch * n, hipMemcpyDeviceToHost, s));
+    if (raw) MICV_HIP(hipMemcpyAsync(raw, draw, sizeof(float) * batch * 3, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_knn_predict_host(micv_ctx *ctx, const float *train, int ntrain, size_t train_stride, const int *train_labels,
+                          const float *test, int ntest, size_t test_stride, int dims, int k, uint32_t flags, int *pred) {
+    HOST_PROLOGUE("micv_knn_predict_host");
+    MICV_REQUIRE(train && train_labels && test && pred && ntrain >= 1 && ntest >= 1 && dims >= 1 &&
+                     dims <= MICV_KNN_MAX_DIMS && train_stride >= sizeof(float) * dims &&
+                     test_stride >= sizeof(float) * dims,
+                 "micv_knn_predict_host: bad argument");
+    const size_t rb = sizeof(float) * dims;
+    DevBuf dt(rb * ntrain), dl(sizeof(int) * ntrain), dq(rb * ntest), dp(sizeof(int) * ntest);
+    MICV_ALLOC_OK(dt); MICV_ALLOC_OK(dl); MICV_ALLOC_OK(dq); MICV_ALLOC_OK(dp);
+    MICV_TRY(up2d(dt.p, train, train_stride, rb, ntrain, s));
+    MICV_HIP(hipMemcpyAsync(dl.p, train_labels, sizeof(int) * ntrain, hipMemcpyHostToDevice, s));
+    MICV_TRY(up2d(dq.p, test, test_stride, rb, ntest, s));
+    MICV_TRY(micv_knn_predict_dev(ctx, dt.as<float>(), ntrain, rb, dl.as<int>(), dq.as<float>(), ntest, rb, dims, k,
+                                  flags, dp.as<int>(), s));
+    MICV_HIP(hipMemcpyAsync(pred, dp.p, sizeof(int) * ntest, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_knn_confusion_host(micv_ctx *ctx, const float *features, int n, size_t stride, int dims, const int *labels,
+                            const int *groups, int num_labels, int num_groups, int k, uint32_t flags, float *confusion,
+                            int *pred, int *left_out) {
+    HOST_PROLOGUE("micv_knn_confusion_host");
+    MICV_REQUIRE(features && labels && confusion && n >= 1 && dims >= 1 && dims <= MICV_KNN_MAX_DIMS &&
+                     stride >= sizeof(float) * dims && num_labels >= 1 && num_labels <= MICV_KNN_MAX_LABELS &&
+                     (!groups || (num_groups >= 1 && num_groups <= MICV_KNN_MAX_GROUPS)),
+                 "micv_knn_confusion_host: bad argument");
+    const size_t rb = sizeof(float) * dims;
+    const int nmat = groups ? num_groups + 1 : 1;
+    const size_t mat_bytes = sizeof(float) * (size_t)nmat * num_labels * num_labels;
+    DevBuf df(rb * n), dl(sizeof(int) * n), dg(groups ? sizeof(int) * n : 1), dp(sizeof(int) * n),
+        dm(mat_bytes + sizeof(int));
+    MICV_ALLOC_OK(df); MICV_ALLOC_OK(dl); MICV_ALLOC_OK(dg); MICV_ALLOC_OK(dp); MICV_ALLOC_OK(dm);
+    MICV_TRY(up2d(df.p, features, stride, rb, n, s));
+    MICV_HIP(hipMemcpyAsync(dl.p, labels, sizeof(int) * n, hipMemcpyHostToDevice, s));
+    if (groups) MICV_HIP(hipMemcpyAsync(dg.p, groups, sizeof(int) * n, hipMemcpyHostToDevice, s));
+    int *dleft = reinterpret_cast<int *>(dm.as<char>() + mat_bytes);
+    MICV_TRY(micv_knn_confusion_dev(ctx, df.as<float>(), n, rb, dims, dl.as<int>(), groups ? dg.as<int>() : nullptr,
+                                    num_labels, num_groups, k, flags, dm.as<float>(), dp.as<int>(), dleft, s));
+    MICV_HIP(hipMemcpyAsync(confusion, dm.p, mat_bytes, hipMemcpyDeviceToHost, s));
+    if (pred) MICV_HIP(hipMemcpyAsync(pred, dp.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+    if (left_out) MICV_HIP(hipMemcpyAsync(left_out, dleft, sizeof(int), hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
 }  // extern "C"

@@ -258,6 +258,10 @@ static Ellipse7 ellipse7() {
     return e;
 }
 
+// The scratch micv_mhi_frame_difference_dev carves from the start of the context arena (its bit-plane words).
+// micv_mhi_history_seq_dev keeps its own planes after this many bytes, so both take the size from here.
+static size_t frame_difference_scratch(int rows, int cols) { return Carver::need((size_t)rows * cdiv(cols, 64), 8); }
+
 }  // namespace micv
 
 using namespace micv;
@@ -279,7 +283,7 @@ int micv_mhi_frame_difference_dev(micv_ctx *ctx, const uint8_t *f1, const uint8_
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int tiles_x = cdiv(cols, 64);
     void *scratch;
-    MICV_TRY(ctx->reserve(Carver::need((size_t)rows * tiles_x, 8), &scratch));
+    MICV_TRY(ctx->reserve(frame_difference_scratch(rows, cols), &scratch));
     unsigned long long *words = static_cast<unsigned long long *>(scratch);
     Taps t, ty;  // cv::Size(width, height): width taps along x, height taps along y
     gaussian_taps(blur_w, blur_sigma, &t);
@@ -337,6 +341,49 @@ int micv_mhi_update_dev(micv_ctx *ctx, uint8_t *history, size_t hstride, const u
     mhi_update_kernel<<<dim3(cdiv(cols, 64), cdiv(rows, 4)), 256, 0, static_cast<hipStream_t>(stream)>>>(
         history, hstride, mask, mstride, rows, cols, tau);
     MICV_LAUNCH_CHECK();
+    return MICV_OK;
+}
+
+
+// mhiHelper's loop (Solution.cpp:16-101): the history and difference planes sit in the scratch after
+// frame_difference_scratch() bytes, the part frameDifference carves from its start; reserving the whole block first
+// keeps frameDifference's own reserve() from moving them.
+int micv_mhi_history_seq_dev(micv_ctx *ctx, const uint8_t *frames, int nframes, size_t frame_pitch, size_t stride,
+                             int rows, int cols, double thresh, int blur_w, int blur_h, double blur_sigma, int tau,
+                             const int *save, int nsave, uint8_t *out, size_t out_pitch, size_t out_stride,
+                             micv_stream stream) {
+    MICV_REQUIRE(ctx && frames && save && out, "micv_mhi_history_seq: null argument");
+    MICV_REQUIRE(nframes >= 2 && nsave >= 1, "micv_mhi_history_seq: need >= 2 frames and >= 1 save number");
+    MICV_REQUIRE(rows > 0 && cols > 0 && stride >= (size_t)cols && out_stride >= (size_t)cols &&
+                     frame_pitch >= stride * (size_t)rows && (nsave == 1 || out_pitch >= out_stride * (size_t)rows),
+                 "micv_mhi_history_seq: bad size / stride / pitch");
+    MICV_REQUIRE(tau > 0, "micv_mhi_history_seq: tau must be > 0");
+    MICV_REQUIRE(blur_w >= 1 && blur_w <= 31 && (blur_w & 1) && blur_h >= 1 && blur_h <= 31 && (blur_h & 1) &&
+                     blur_sigma > 0,
+                 "micv_mhi_history_seq: blur %dx%d / sigma %g not supported (odd sizes <= 31, sigma > 0)", blur_w,
+                 blur_h, blur_sigma);
+    int last = 0;
+    for (int i = 0; i < nsave; i++) {
+        MICV_REQUIRE(save[i] >= 1 && save[i] <= nframes - 1, "micv_mhi_history_seq: save number %d outside 1..%d",
+                     save[i], nframes - 1);
+        last = save[i] > last ? save[i] : last;
+    }
+    MICV_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t words = frame_difference_scratch(rows, cols), plane = Carver::need((size_t)rows * cols, 1);
+    void *scratch;
+    MICV_TRY(ctx->reserve(words + 2 * plane, &scratch));
+    uint8_t *hist = static_cast<uint8_t *>(scratch) + words, *diff = hist + plane;
+    MICV_HIP(hipMemsetAsync(hist, 0, (size_t)rows * cols, s));
+    for (int f = 1; f <= last; f++) {
+        MICV_TRY(micv_mhi_frame_difference_dev(ctx, frames + (size_t)(f - 1) * frame_pitch, frames + (size_t)f * frame_pitch,
+                                               rows, cols, stride, thresh, blur_w, blur_h, blur_sigma, diff, cols, stream));
+        MICV_TRY(micv_mhi_update_dev(ctx, hist, cols, diff, cols, rows, cols, tau, stream));
+        for (int i = 0; i < nsave; i++)
+            if (save[i] == f)
+                MICV_HIP(hipMemcpy2DAsync(out + (size_t)i * out_pitch, out_stride, hist, cols, cols, rows,
+                                          hipMemcpyDeviceToDevice, s));
+    }
     return MICV_OK;
 }
 

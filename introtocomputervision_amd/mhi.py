@@ -116,3 +116,34 @@ def energyFromHistory(mhi, ctx=None):
     check(lib.micv_mhi_energy_dev(_ctx_for(mhi, ctx).handle, mhi.data_ptr(), rows, cols, mhi.stride(0),
                                   mei.data_ptr(), cols, _stream(mhi)))
     return mei
+
+
+def historySequence(frames, thresh, blurSize, blurSigma, tau, saveFrames, ctx=None):
+    """mhiHelper's loop (ps7_cpp/src/Solution.cpp:16-101) over one video: frames is [F, rows, cols] uint8; the history
+    after update number j (frameDifference(frame j-1, frame j), then calcMotionHistory) is returned for every j in
+    saveFrames (1..F-1, mhiHelper's frameNum), stacked as [len(saveFrames), rows, cols] uint8."""
+    import numpy as np
+    bw, bh = _blur_wh(blurSize)
+    save = np.ascontiguousarray(np.asarray(saveFrames, dtype=np.int32).reshape(-1))
+    if isinstance(frames, np.ndarray):
+        if frames.ndim != 3 or frames.dtype != np.uint8:
+            raise ValueError("frames: need a [F, rows, cols] uint8 array")
+        f = frames if (frames.strides[2] == 1 and min(frames.strides) > 0) else np.ascontiguousarray(frames)
+        F, rows, cols = f.shape
+        out = np.empty((save.size, rows, cols), np.uint8)
+        check(lib.micv_mhi_history_seq_host((ctx or _host_ctx()).handle, f.ctypes.data, F, f.strides[0], f.strides[1],
+                                            rows, cols, float(thresh), bw, bh, float(blurSigma), int(tau),
+                                            save.ctypes.data, save.size, out.ctypes.data, out.strides[0],
+                                            out.strides[1]))
+        return out
+    import torch
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dim() == 3
+            and frames.dtype == torch.uint8 and frames.stride(2) == 1):
+        raise ValueError("frames: need a [F, rows, cols] uint8 CUDA tensor with unit column stride")
+    F, rows, cols = frames.shape
+    out = torch.empty((save.size, rows, cols), dtype=torch.uint8, device=frames.device)
+    check(lib.micv_mhi_history_seq_dev(_ctx_for(frames, ctx).handle, frames.data_ptr(), F, frames.stride(0),
+                                       frames.stride(1), rows, cols, float(thresh), bw, bh, float(blurSigma), int(tau),
+                                       save.ctypes.data, save.size, out.data_ptr(), rows * cols, cols,
+                                       _stream(frames)))
+    return out

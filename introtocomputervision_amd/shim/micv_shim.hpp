@@ -10,6 +10,7 @@
 //   ParticleFilter  ProblemSets/ps6_cpp/include/ParticleFilter.h (the class, in the global namespace)
 //   cuda:: / serial::  ps2_cpp/include/DisparitySSD.h:18-43, DisparityNCorr.h:19-44,
 //                      ps1_cpp/src/Hough.h:22-84
+//   mhi::, moments::, matching::  ps7_cpp/include/{MotionHistory,Moments,Matching}.h
 // Inputs are const references and never retained; outputs are (re)allocated by the callee like
 // the reference does (Mat::create / assignment of a fresh Mat).  Errors: the reference asserts or
 // exit(-1)s (CudaCommon.cuh:13-22); the shim throws std::runtime_error carrying micv_last_error().
@@ -20,6 +21,9 @@
 
 #include <cmath>
 #include <cstring>
+#include <fstream>
+#include <algorithm>
+#include <cstdio>
 #include <functional>
 #include <iostream>
 #include <memory>
@@ -735,6 +739,128 @@ inline void energyFromHistory(const std::vector<Mat> &mhis, std::vector<Mat> &me
     }
 }
 }  // namespace mhi
+
+namespace moments {  // ProblemSets/ps7_cpp/include/Moments.h:9-12, lib/Moments.cpp:7-67
+using micv_shim::Mat;
+// One image, CV_8UC1 or CV_32FC1 (the driver passes its cv::normalize-d MHIs as CV_32FC1 and its MEIs as CV_8UC1).
+// The arithmetic is mi_cv.h's "ps7: central moments" with the reference's xFull - yBar kept as written.
+inline std::vector<std::pair<float, float>> centralMoment(const Mat &img,
+                                                          const std::vector<std::pair<int, int>> &momentOrders) {
+    micv_shim::require(img.type() == micv_shim::U8 || img.type() == micv_shim::F32,
+                       "moments::centralMoment: CV_8UC1 or CV_32FC1 expected");
+    std::vector<std::pair<float, float>> out;
+    const size_t n = momentOrders.size();
+    std::vector<int> orders;
+    for (const auto &o : momentOrders) {
+        orders.push_back(o.first);
+        orders.push_back(o.second);
+    }
+    std::vector<float> mu(MICV_MOMENTS_MAX_ORDERS), eta(MICV_MOMENTS_MAX_ORDERS);
+    for (size_t j0 = 0; j0 < n; j0 += MICV_MOMENTS_MAX_ORDERS) {  // the C ABI takes up to 16 orders per call
+        const int m = (int)std::min<size_t>(MICV_MOMENTS_MAX_ORDERS, n - j0);
+        micv_shim::check(micv_central_moments_host(micv_shim::context(), img.data, 1, 0, img.step, img.rows, img.cols,
+                                                   img.type() == micv_shim::F32 ? MICV_MOMENTS_F32 : MICV_MOMENTS_U8,
+                                                   orders.data() + 2 * j0, m, 0, mu.data(), eta.data(), nullptr));
+        for (int j = 0; j < m; j++) out.emplace_back(mu[j], eta[j]);
+    }
+    return out;
+}
+}  // namespace moments
+
+namespace matching {  // ProblemSets/ps7_cpp/include/Matching.h:5-27, lib/Matching.cpp (k = 3, three actions)
+using micv_shim::Mat;
+namespace detail {
+constexpr int kLabels = 3, kK = 3;  // Matching.cpp: cv::Mat::zeros(3, 3, CV_32F), findNearest(.., 3, ..)
+// features CV_32FC1 (rows = samples); labels CV_32FC1 (arrangeTrainingData's convertTo) or CV_32SC1, one column
+inline std::vector<int32_t> labels_of(const Mat &features, const Mat &labels) {
+    micv_shim::require(features.type() == micv_shim::F32 && features.cols >= 1 && features.cols <= MICV_KNN_MAX_DIMS,
+                       "matching: CV_32FC1 features of 1..64 columns expected");
+    micv_shim::require(labels.rows == features.rows && labels.cols == 1 &&
+                           (labels.type() == micv_shim::F32 || labels.type() == micv_shim::S32),
+                       "matching: one CV_32FC1 / CV_32SC1 label per feature row expected");
+    std::vector<int32_t> out(labels.rows);
+    for (int r = 0; r < labels.rows; r++) {
+        if (labels.type() == micv_shim::S32) {
+            out[r] = labels.ptr<int32_t>(r)[0];
+        } else {
+            const float v = labels.ptr<float>(r)[0];
+            micv_shim::require(v == std::nearbyint(v) && std::fabs(v) < 1e9f, "matching: labels must be integers");
+            out[r] = (int32_t)v;
+        }
+    }
+    return out;
+}
+inline Mat matrix(const float *m) {
+    Mat c(kLabels, kLabels, micv_shim::F32);
+    for (int r = 0; r < kLabels; r++)
+        for (int x = 0; x < kLabels; x++) c.ptr<float>(r)[x] = m[r * kLabels + x];
+    return c;
+}
+}  // namespace detail
+
+// Leave-one-out; rows whose label or vote is outside 1..3 are left out of the matrix (the reference asserts).
+inline void naiveConfusionMatrix(const Mat &features, const Mat &labels, Mat &confusion) {
+    const std::vector<int32_t> lab = detail::labels_of(features, labels);
+    float m[detail::kLabels * detail::kLabels];
+    micv_shim::check(micv_knn_confusion_host(micv_shim::context(), features.ptr<float>(), features.rows, features.step,
+                                             features.cols, lab.data(), nullptr, detail::kLabels, 0, detail::kK, 0, m,
+                                             nullptr, nullptr));
+    confusion = detail::matrix(m);
+}
+
+// Leave-one-person-out for persons 1..numPeople; appends numPeople matrices and then their average, like the reference.
+inline void confusionMatrix(const Mat &features, const Mat &labels, const Mat &people, const size_t numPeople,
+                            std::vector<Mat> &confusions) {
+    const std::vector<int32_t> lab = detail::labels_of(features, labels);
+    micv_shim::require(people.type() == micv_shim::S32 && people.rows == features.rows && people.cols == 1,
+                       "matching::confusionMatrix: one CV_32SC1 person id per feature row expected");
+    micv_shim::require(numPeople >= 1 && numPeople <= MICV_KNN_MAX_GROUPS, "matching::confusionMatrix: 1..32 people");
+    std::vector<int32_t> grp(people.rows);
+    for (int r = 0; r < people.rows; r++) grp[r] = people.ptr<int32_t>(r)[0];
+    const int L2 = detail::kLabels * detail::kLabels;
+    std::vector<float> m((numPeople + 1) * L2);
+    micv_shim::check(micv_knn_confusion_host(micv_shim::context(), features.ptr<float>(), features.rows, features.step,
+                                             features.cols, lab.data(), grp.data(), detail::kLabels, (int)numPeople,
+                                             detail::kK, 0, m.data(), nullptr, nullptr));
+    for (size_t g = 0; g <= numPeople; g++) confusions.push_back(detail::matrix(m.data() + g * L2));
+}
+
+// No gnuplot: prints the title and the numbers the plot labels ('%.2f', expected action = row, predicted = column) to
+// stdout and, when fileName is given, writes the heat image (white -> green, 32 x 32 pixels per cell) as a binary PPM
+// at fileName with its extension replaced by ".ppm".
+inline void plotConfusionMatrix(const Mat &confusion, const std::string &title, const std::string &fileName = "") {
+    micv_shim::require(confusion.type() == micv_shim::F32, "matching::plotConfusionMatrix: CV_32FC1 expected");
+    std::cout << title << "\n";
+    for (int y = 0; y < confusion.rows; y++) {
+        std::cout << "action " << y + 1 << ":";
+        for (int x = 0; x < confusion.cols; x++) {
+            char b[32];
+            std::snprintf(b, sizeof b, " %.2f", (double)confusion.ptr<float>(y)[x]);
+            std::cout << b;
+        }
+        std::cout << "\n";
+    }
+    if (fileName.empty()) return;
+    const size_t dot = fileName.find_last_of('.'), slash = fileName.find_last_of('/');
+    const std::string path =
+        (dot != std::string::npos && (slash == std::string::npos || dot > slash) ? fileName.substr(0, dot) : fileName) +
+        ".ppm";
+    const int cell = 32, W = confusion.cols * cell, H = confusion.rows * cell;
+    std::vector<unsigned char> px((size_t)W * H * 3);
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            float v = confusion.ptr<float>(y / cell)[x / cell];
+            v = std::isfinite(v) ? std::min(std::max(v, 0.f), 1.f) : 0.f;  // palette (0 'white', 1 'green')
+            unsigned char *p = &px[((size_t)y * W + x) * 3];
+            p[0] = p[2] = (unsigned char)std::lrint(255.0 * (1.0 - v));
+            p[1] = 255;
+        }
+    std::ofstream f(path, std::ios::binary);
+    f << "P6\n" << W << " " << H << "\n255\n";
+    f.write(reinterpret_cast<const char *>(px.data()), (std::streamsize)px.size());
+    micv_shim::require((bool)f, "matching::plotConfusionMatrix: cannot write the image");
+}
+}  // namespace matching
 
 namespace sol {
 using micv_shim::Mat;

@@ -271,6 +271,23 @@ inline Mat normalize_minmax_u8(const Mat &src) {
     return dst;
 }
 
+// cv::normalize(src, dst, 1.0, 0.0, NORM_INF, CV_32FC1) of a CV_8UC1 image, as ps7's driver applies it to its MHIs
+// (ps7_cpp/src/Solution.cpp:243-245): scale = 1.0 / max in double (0 when max <= DBL_EPSILON), then convertTo with a
+// float work type, dst = (float)src * (float)scale.  Bit for bit what micv_central_moments_* do under
+// MICV_MOMENTS_NORM_INF.
+inline Mat normalize_inf_f32(const Mat &src) {
+    micv_shim::require(src.type() == micv_shim::U8, "normalize_inf_f32: CV_8UC1 expected");
+    int mx = 0;
+    for (int y = 0; y < src.rows; y++)
+        for (int x = 0; x < src.cols; x++) mx = std::max(mx, (int)src.at<unsigned char>(y, x));
+    const double norm = mx;
+    const float s = (float)(norm > DBL_EPSILON ? 1.0 / norm : 0.0);
+    Mat dst(src.rows, src.cols, micv::CV_32FC1);
+    for (int y = 0; y < src.rows; y++)
+        for (int x = 0; x < src.cols; x++) dst.at<float>(y, x) = (float)src.at<unsigned char>(y, x) * s;
+    return dst;
+}
+
 // cv::applyColorMap(src, dst, COLORMAP_JET): CV_8UC1 -> CV_8UC3 (B, G, R).
 inline Mat apply_colormap_jet(const Mat &src) {
     micv_shim::require(src.type() == micv::CV_8UC1, "applyColorMap: CV_8UC1 expected");
