@@ -848,6 +848,116 @@ int micv_knn_confusion_host(micv_ctx *ctx, const float *features, int n, size_t 
                             const int *groups, int num_labels, int num_groups, int k, uint32_t flags, float *confusion,
                             int *pred, int *left_out);
 
+/* ------------------------------------------------------------- ps3: geometry -------- */
+
+/* Camera calibration and the fundamental matrix of ps3 (ps3_cpp/lib/Calibration.cpp, lib/Fundamental.cpp and the
+ * driver ps3_cpp/src/Solution.cpp), batched: T systems share their point arrays and differ in an index list, one wave
+ * per system, nothing gathered on the host.  Points are ROWS here: pts2d [n][2], pts3d [n][3] f32 (the reference's
+ * cv::Mats are 2 x n / 3 x n; the Python layer and the shim transpose).  indices is [T][stride] int32; NULL (T = 1
+ * only) means 0, 1, 2, ...  Stream-ordered, no host sync; bad arguments return MICV_EINVAL before anything is
+ * enqueued.  An index outside [0, n) (or a kcount outside [0, k]) cannot be seen on the host by a _dev entry: the
+ * system's outputs are NaN and *status (device int32, zeroed by the call) becomes 1; the _host entries check the lists
+ * first and return MICV_EINVAL with every output untouched.
+ *
+ * Arithmetic contract.  R is float, or double with MICV_GEOM_F64: the same operations in the same order, inputs still
+ * f32, every output rounded once to f32 (residuals stay double).  No fused multiply-add.
+ *   normal equations   S = A^T A and A^T b are summed entry by entry, from 0, over the rows of A in order (constraint
+ *         0 first, its x row before its y row), s = fl(s + fl(a_r * a_c)), zero entries of A included (0 * inf = NaN
+ *         as written); A is never formed.  Calibration rows: [X Y Z 1 0 0 0 0 (-x)X (-x)Y (-x)Z | x] and
+ *         [0 0 0 0 X Y Z 1 (-y)X (-y)Y (-y)Z | y]; fundamental rows [u u', v u', u', u v', v v', v', u, v | -1]
+ *         with (u, v) from image A and (u', v') from image B.
+ *   LDL^T  diagonal pivoting: at step p the first largest |S[i][i]|, i >= p (a NaN is never larger), rows and columns
+ *         swapped; S[i][j] -= fl(S[p][max(i,j)] / d) * S[p][min(i,j)] for i, j > p and b[i] -= fl(S[p][i] / d) * b[p];
+ *         L[i][p] = fl(S[p][i] / d).  z[p] = b[p] / d[p]; x[p] = z[p] - L[p+1][p] x[p+1] - .. (ascending), p
+ *         descending; the permutation undone.  No threshold: a zero pivot gives inf / NaN.  A 1 is appended.
+ *   trial residual (Solution.cpp:243-318)  per test point p_r = (R)(((m_r0 X + m_r1 Y) + m_r2 Z) + m_r3 * 1) with
+ *         double products and sums (the gemm rule of the RANSAC block), w = (R)(1.0 / (double)p_2), u = fl(p_0 * w),
+ *         v = fl(p_1 * w) (cv::Mat / scalar multiplies by the reciprocal), d = sqrt(D(u - x)^2 + D(v - y)^2) in double
+ *         with D() the R difference widened; residual = (d_0 + d_1 + ..) / (double)j from 0.0 in order; j = 0 gives
+ *         NaN.  With MICV_GEOM_F64 the unrounded double M is projected.
+ *   arg-min  per group and overall, the first trial whose residual is strictly below every earlier one and below
+ *         DBL_MAX (the reference's start value): NaN and +inf never win.  No winner: index -1, residual DBL_MAX, M = 0.
+ *   SVD   one-sided (Hestenes) Jacobi on the columns of A (calibration: the rows above with -x / -y as 12th entry),
+ *         V = I.  Pairs (p, q), p < q, in the cyclic order (0,1), (0,2), .., (10,11).  alpha = S a_p^2, beta = S a_q^2,
+ *         gamma = S a_p a_q: 64 serial partials (partial l sums rows l, l + 64, .. from 0) joined by
+ *         v_l = v_l + v_(l xor m) for m = 32, 16, 8, 4, 2, 1.  The pair rotates when |gamma| > eps sqrt(alpha beta),
+ *         eps = 1e-7f (R = float) or 1e-15 (double): zeta = (beta - alpha) / (2 gamma),
+ *         t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)) with sign(0) = +1, c = 1 / sqrt(1 + t^2), s = c t,
+ *         a_p' = c a_p - s a_q, a_q' = s a_p + c a_q, the same on the columns of V.  The loop ends after a sweep
+ *         without a rotation or after 30 sweeps.  The answer is the column of V whose column of A has the smallest
+ *         squared norm (summed the same way), the first one on ties; unit norm, sign as it falls.
+ *   rank reduction  the same Jacobi on the 3 x 3 matrix; the column of the rotated A with the smallest norm is set to
+ *         zero and out[r][c] = ((0 + a_r0 v_c0) + a_r1 v_c1) + a_r2 v_c2 (U Sigma V^T with the smallest sigma = 0).
+ *   3 x 3 products  double accumulation from the first product, ascending, one rounding to R.
+ *   normalised chain (Solution.cpp:381-445)  mean = (R)(s / n), s a double chain over R partial sums of four
+ *         (cv::mean); m = max(1, |coordinates|) (the row of ones takes part; NaN ignored); T = scale * offset with
+ *         scale = diag(w, w, 1), w = (R)(1.0 / (double)m), offset = [1 0 -mean_x; 0 1 -mean_y; 0 0 1]; the points
+ *         T [x y 1]^T; F_Hat = rank reduction of the normal-equation solve; F = (T_b^T F_Hat) T_a.
+ *   epipolar end points (Solution.cpp:124-163, :343-362)  side 0: l = (p^T F)^T for p of image B, lines in image A;
+ *         side 1: l = F p for p of image A.  I_L = (0,0,1) x (0,rows-1,1), I_R = (cols-1,0,1) x (cols-1,rows-1,1);
+ *         P = l x I (cv::Mat::cross in R), then P * (R)(1.0 / (double)P_2).  out [n][6] = P_iL, P_iR.
+ *   camera centre (Solution.cpp:320-326)  Q^-1 by the closed form of the RANSAC block (determinant and cofactors in
+ *         double, each rounded to R, zeros when det = 0), centre_r = (R)(-1.0 * ((q_r0 m_03 + q_r1 m_13) + q_r2 m_23)).
+ * Degenerate systems (too few constraints, repeated points, NaN / inf points) run as written and give inf / NaN.
+ * Limits: n <= 2^24, j <= 64, at most 64 groups, k <= 1024 for the SVD.  Shared scratch: one call at a time per
+ * context, as everywhere. */
+#define MICV_GEOM_F64 1u
+
+/* calib::solveLeastSquares for T index subsets, the trial of Solution.cpp:243-318 and its arg-min in ONE call.
+ * Trial t takes indices[t][0 .. kc-1] as constraints, kc = kcount ? kcount[t] : k (kcount device, each <= k), and the
+ * next j entries as test points: the first kc + j entries of a permutation, as genUniqueRands hands them out.
+ * group_sizes (HOST, G entries summing to T, or NULL with G = 0) are the reference's set sizes' trial counts.
+ * Out (device): M [T][12] f32, residual [T] f64, and, unless the three are NULL, G + 1 arg-min records (the groups,
+ * then all trials): best_idx [G+1] i32, best_res [G+1] f64, best_M [G+1][12] f32.  T = 1, j = 0, indices NULL is the
+ * plain calib::solveLeastSquares of the first k points. */
+int micv_calib_ls_trials_dev(micv_ctx *ctx, const float *pts2d, const float *pts3d, int n, const int32_t *indices,
+                             int stride, int k, int j, int T, const int32_t *kcount, const int *group_sizes, int G,
+                             uint32_t flags, float *M, double *residual, int32_t *best_idx, double *best_res,
+                             float *best_M, int32_t *status, micv_stream stream);
+int micv_calib_ls_trials_host(micv_ctx *ctx, const float *pts2d, const float *pts3d, int n, const int32_t *indices,
+                              int stride, int k, int j, int T, const int32_t *kcount, const int *group_sizes, int G,
+                              uint32_t flags, float *M, double *residual, int32_t *best_idx, double *best_res,
+                              float *best_M);
+/* calib::solveSVD for T index subsets of k points each: M [T][12]. */
+int micv_calib_svd_dev(micv_ctx *ctx, const float *pts2d, const float *pts3d, int n, const int32_t *indices, int stride,
+                       int k, int T, uint32_t flags, float *M, int32_t *status, micv_stream stream);
+int micv_calib_svd_host(micv_ctx *ctx, const float *pts2d, const float *pts3d, int n, const int32_t *indices, int stride,
+                        int k, int T, uint32_t flags, float *M);
+/* fundamental::solveLeastSquares for T index subsets of k correspondences: F [T][9]. */
+int micv_fundamental_ls_dev(micv_ctx *ctx, const float *ptsA, const float *ptsB, int n, const int32_t *indices,
+                            int stride, int k, int T, uint32_t flags, float *F, int32_t *status, micv_stream stream);
+int micv_fundamental_ls_host(micv_ctx *ctx, const float *ptsA, const float *ptsB, int n, const int32_t *indices,
+                             int stride, int k, int T, uint32_t flags, float *F);
+/* fundamental::rankReduce of T 3 x 3 matrices (row-major). */
+int micv_fundamental_rank_reduce_dev(micv_ctx *ctx, const float *F, int T, uint32_t flags, float *out,
+                                     micv_stream stream);
+int micv_fundamental_rank_reduce_host(micv_ctx *ctx, const float *F, int T, uint32_t flags, float *out);
+/* The extra-credit chain: Ta, Tb, Fhat, F, 9 f32 each. */
+int micv_fundamental_normalized_dev(micv_ctx *ctx, const float *ptsA, const float *ptsB, int n, uint32_t flags,
+                                    float *Ta, float *Tb, float *Fhat, float *F, micv_stream stream);
+int micv_fundamental_normalized_host(micv_ctx *ctx, const float *ptsA, const float *ptsB, int n, uint32_t flags,
+                                     float *Ta, float *Tb, float *Fhat, float *F);
+int micv_epipolar_endpoints_dev(micv_ctx *ctx, const float *F, const float *pts, int n, int side, int rows, int cols,
+                                uint32_t flags, float *out, micv_stream stream);
+int micv_epipolar_endpoints_host(micv_ctx *ctx, const float *F, const float *pts, int n, int side, int rows, int cols,
+                                 uint32_t flags, float *out);
+/* Camera centres of T projection matrices M [T][12]: center [T][3]. */
+int micv_camera_center_dev(micv_ctx *ctx, const float *M, int T, uint32_t flags, float *center, micv_stream stream);
+int micv_camera_center_host(micv_ctx *ctx, const float *M, int T, uint32_t flags, float *center);
+
+/* genUniqueRands (Solution.cpp:68-96) on the shared engine of the RANSAC block: per trial a FRESH iota 0 .. n-1,
+ * std::shuffle'd (libstdc++) by the engine -- unlike ransac::solve's persistent vector.  out [trials][n] receives the
+ * whole permutations (the first k are the constraints, the next j the test points); the engine advances by `trials`
+ * shuffles.  Host-side, no device work. */
+int micv_geom_trial_indices(micv_ransac_rng *rng, int64_t n, int trials, int32_t *out);
+/* For batches too large to draw on the host: `count` distinct indices of [0, n) per trial, on the device, NOT the
+ * reference's sequence.  Trial t, entry e = 0 .. count-1, attempt a = 0, 1, ..:
+ *     r = splitmix64(seed ^ ((uint64)t << 32 | (uint64)e << 20 | (a & 0xFFFFF))), idx = ((r >> 32) * n) >> 32
+ * (splitmix64 as in the RANSAC block); the first attempt whose idx differs from the trial's earlier entries is entry e.
+ * out [T][count] i32 (device); count <= min(n, 4096), T < 2^31. */
+int micv_geom_sample_indices_dev(micv_ctx *ctx, uint64_t seed, int n, int count, int64_t T, int32_t *out,
+                                 micv_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

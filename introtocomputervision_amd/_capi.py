@@ -37,6 +37,7 @@ MOMENTS_NORM_INF, MOMENTS_Y_FIXED = 1, 2
 MOMENTS_MAX_ORDERS, MOMENTS_MAX_ORDER = 16, 8
 KNN_F64_ACC = 1
 KNN_MAX_DIMS, KNN_MAX_K, KNN_MAX_LABELS, KNN_MAX_GROUPS = 64, 32, 16, 32
+GEOM_F64 = 1  # ps3 (mi_cv.h): geometry
 # micv_ctx_set_option (include/mi_cv.h): none of these changes a result
 (OPT_LK_STREAM_GROUPS, OPT_LK_FORCE_GENERIC, OPT_LK_NARROW_TILES, OPT_SOBEL_GENERIC, OPT_HARRIS_GENERIC,
  OPT_NMS_SCAN, OPT_STEREO_ROWS, OPT_LK_CHAIN, OPT_LK_SHORT_TILES, OPT_LK_STREAM, OPT_LK_TALL_TILES,
@@ -199,6 +200,23 @@ SIGNATURES = {
     "micv_knn_predict_host": (i32, [vp, vp, i32, sz, vp, vp, i32, sz, i32, i32, u32, vp]),
     "micv_knn_confusion_dev": (i32, [vp, vp, i32, sz, i32, vp, vp, i32, i32, i32, u32, vp, vp, vp, vp]),
     "micv_knn_confusion_host": (i32, [vp, vp, i32, sz, i32, vp, vp, i32, i32, i32, u32, vp, vp, vp]),
+    # ps3: geometry
+    "micv_calib_ls_trials_dev": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, u32, vp, vp, vp, vp, vp, vp, vp]),
+    "micv_calib_ls_trials_host": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, u32, vp, vp, vp, vp, vp]),
+    "micv_calib_svd_dev": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, u32, vp, vp, vp]),
+    "micv_calib_svd_host": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, u32, vp]),
+    "micv_fundamental_ls_dev": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, u32, vp, vp, vp]),
+    "micv_fundamental_ls_host": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, u32, vp]),
+    "micv_fundamental_rank_reduce_dev": (i32, [vp, vp, i32, u32, vp, vp]),
+    "micv_fundamental_rank_reduce_host": (i32, [vp, vp, i32, u32, vp]),
+    "micv_fundamental_normalized_dev": (i32, [vp, vp, vp, i32, u32, vp, vp, vp, vp, vp]),
+    "micv_fundamental_normalized_host": (i32, [vp, vp, vp, i32, u32, vp, vp, vp, vp]),
+    "micv_epipolar_endpoints_dev": (i32, [vp, vp, vp, i32, i32, i32, i32, u32, vp, vp]),
+    "micv_epipolar_endpoints_host": (i32, [vp, vp, vp, i32, i32, i32, i32, u32, vp]),
+    "micv_camera_center_dev": (i32, [vp, vp, i32, u32, vp, vp]),
+    "micv_camera_center_host": (i32, [vp, vp, i32, u32, vp]),
+    "micv_geom_trial_indices": (i32, [vp, i64, i32, vp]),
+    "micv_geom_sample_indices_dev": (i32, [vp, C.c_uint64, i32, i32, i64, vp, vp]),
 }
 
 MISSING = []

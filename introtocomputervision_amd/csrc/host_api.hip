@@ -940,4 +940,167 @@ int micv_knn_confusion_host(micv_ctx *ctx, const float *features, int n, size_t 
     return MICV_OK;
 }
 
+// ps3: geometry.  The index lists are checked here, before anything is uploaded.
+static int geom_indices_ok(const char *fn, const int32_t *indices, int stride, int T, const int32_t *kcount, int k,
+                           int j, int n) {
+    if (!indices) return MICV_OK;
+    for (int t = 0; t < T; t++) {
+        const int kc = kcount ? kcount[t] : k;
+        MICV_REQUIRE(kc >= 0 && kc <= k, "%s: kcount[%d] = %d outside [0, %d]", fn, t, kc, k);
+        for (int i = 0; i < kc + j; i++) {
+            const int32_t v = indices[(size_t)t * stride + i];
+            MICV_REQUIRE(v >= 0 && v < n, "%s: index [%d][%d] = %d outside [0, %d)", fn, t, i, v, n);
+        }
+    }
+    return MICV_OK;
+}
+
+int micv_calib_ls_trials_host(micv_ctx *ctx, const float *pts2d, const float *pts3d, int n, const int32_t *indices,
+                              int stride, int k, int j, int T, const int32_t *kcount, const int *group_sizes, int G,
+                              uint32_t flags, float *M, double *residual, int32_t *best_idx, double *best_res,
+                              float *best_M) {
+    HOST_PROLOGUE("micv_calib_ls_trials_host");
+    MICV_REQUIRE(pts2d && pts3d && M && residual, "micv_calib_ls_trials_host: null argument");
+    MICV_REQUIRE(n >= 1 && n <= 1 << 24 && k >= 0 && j >= 0 && j <= 64 && (int64_t)k + j <= n && T >= 1 &&
+                     (indices ? stride >= k + j : (T == 1 && !kcount)) && G >= 0 && G <= 64 && (G == 0) == !group_sizes,
+                 "micv_calib_ls_trials_host: bad n %d, k %d, j %d, T %d, stride %d or G %d", n, k, j, T, stride, G);
+    if (group_sizes) {
+        int64_t sum = 0;
+        for (int i = 0; i < G; i++) sum += group_sizes[i] < 0 ? -((int64_t)1 << 40) : group_sizes[i];
+        MICV_REQUIRE(sum == T && best_idx, "micv_calib_ls_trials_host: group sizes do not sum to T = %d", T);
+    }
+    MICV_REQUIRE((best_idx != nullptr) == (best_res != nullptr) && (best_idx != nullptr) == (best_M != nullptr) &&
+                     !(flags & ~MICV_GEOM_F64),
+                 "micv_calib_ls_trials_host: best_idx, best_res and best_M go together; flags %u", flags);
+    MICV_TRY(geom_indices_ok("micv_calib_ls_trials_host", indices, stride, T, kcount, k, j, n));
+    const size_t ni = indices ? (size_t)T * stride : 1, nr = (size_t)G + 1;
+    DevBuf d2((size_t)n * 8), d3((size_t)n * 12), di(ni * 4), dk((size_t)T * 4), dM((size_t)T * 48), dr((size_t)T * 8),
+        dbi(nr * 4), dbr(nr * 8), dbm(nr * 48), dst(4);
+    MICV_ALLOC_OK(d2); MICV_ALLOC_OK(d3); MICV_ALLOC_OK(di); MICV_ALLOC_OK(dk); MICV_ALLOC_OK(dM); MICV_ALLOC_OK(dr);
+    MICV_ALLOC_OK(dbi); MICV_ALLOC_OK(dbr); MICV_ALLOC_OK(dbm); MICV_ALLOC_OK(dst);
+    MICV_HIP(hipMemcpyAsync(d2.p, pts2d, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(d3.p, pts3d, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    if (indices) MICV_HIP(hipMemcpyAsync(di.p, indices, ni * 4, hipMemcpyHostToDevice, s));
+    if (kcount) MICV_HIP(hipMemcpyAsync(dk.p, kcount, (size_t)T * 4, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_calib_ls_trials_dev(ctx, d2.as<float>(), d3.as<float>(), n, indices ? di.as<int32_t>() : nullptr,
+                                      stride, k, j, T, kcount ? dk.as<int32_t>() : nullptr, group_sizes, G, flags,
+                                      dM.as<float>(), dr.as<double>(), best_idx ? dbi.as<int32_t>() : nullptr,
+                                      best_idx ? dbr.as<double>() : nullptr, best_idx ? dbm.as<float>() : nullptr,
+                                      dst.as<int32_t>(), s));
+    MICV_HIP(hipMemcpyAsync(M, dM.p, (size_t)T * 48, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipMemcpyAsync(residual, dr.p, (size_t)T * 8, hipMemcpyDeviceToHost, s));
+    if (best_idx) {
+        MICV_HIP(hipMemcpyAsync(best_idx, dbi.p, nr * 4, hipMemcpyDeviceToHost, s));
+        MICV_HIP(hipMemcpyAsync(best_res, dbr.p, nr * 8, hipMemcpyDeviceToHost, s));
+        MICV_HIP(hipMemcpyAsync(best_M, dbm.p, nr * 48, hipMemcpyDeviceToHost, s));
+    }
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+// The shape shared by the SVD and the fundamental solve: two point arrays, an index list, `per` floats out per system.
+extern "C++" template <typename Fn>
+static int geom_solve_host(micv_ctx *ctx, hipStream_t s, const char *fn, const float *pa, size_t abytes, const float *pb,
+                           size_t bbytes, int n, const int32_t *indices, int stride, int k, int T, int per, float *out,
+                           Fn call) {
+    MICV_TRY(geom_indices_ok(fn, indices, stride, T, nullptr, k, 0, n));
+    const size_t ni = indices ? (size_t)T * stride : 1;
+    DevBuf da(abytes), db(bbytes), di(ni * 4), dout((size_t)T * per * 4), dst(4);
+    MICV_ALLOC_OK(da); MICV_ALLOC_OK(db); MICV_ALLOC_OK(di); MICV_ALLOC_OK(dout); MICV_ALLOC_OK(dst);
+    MICV_HIP(hipMemcpyAsync(da.p, pa, abytes, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(db.p, pb, bbytes, hipMemcpyHostToDevice, s));
+    if (indices) MICV_HIP(hipMemcpyAsync(di.p, indices, ni * 4, hipMemcpyHostToDevice, s));
+    MICV_TRY(call(da.as<float>(), db.as<float>(), indices ? di.as<int32_t>() : nullptr, dout.as<float>(),
+                  dst.as<int32_t>()));
+    MICV_HIP(hipMemcpyAsync(out, dout.p, (size_t)T * per * 4, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_calib_svd_host(micv_ctx *ctx, const float *pts2d, const float *pts3d, int n, const int32_t *indices, int stride,
+                        int k, int T, uint32_t flags, float *M) {
+    HOST_PROLOGUE("micv_calib_svd_host");
+    MICV_REQUIRE(pts2d && pts3d && M, "micv_calib_svd_host: null argument");
+    MICV_REQUIRE(!(flags & ~MICV_GEOM_F64) && n >= 1 && n <= 1 << 24 && k >= 1 && k <= 1024 && k <= n && T >= 1 &&
+                     (indices ? stride >= k : T == 1),
+                 "micv_calib_svd_host: bad flags %u, n %d, k %d, T %d or stride %d", flags, n, k, T, stride);
+    return geom_solve_host(ctx, s, "micv_calib_svd_host", pts2d, (size_t)n * 8, pts3d, (size_t)n * 12, n, indices, stride,
+                           k, T, 12, M, [&](float *a, float *b, int32_t *i, float *o, int32_t *st) {
+                               return micv_calib_svd_dev(ctx, a, b, n, i, stride, k, T, flags, o, st, s);
+                           });
+}
+
+int micv_fundamental_ls_host(micv_ctx *ctx, const float *ptsA, const float *ptsB, int n, const int32_t *indices,
+                             int stride, int k, int T, uint32_t flags, float *F) {
+    HOST_PROLOGUE("micv_fundamental_ls_host");
+    MICV_REQUIRE(ptsA && ptsB && F, "micv_fundamental_ls_host: null argument");
+    MICV_REQUIRE(!(flags & ~MICV_GEOM_F64) && n >= 1 && n <= 1 << 24 && k >= 0 && k <= n && T >= 1 &&
+                     (indices ? stride >= k : T == 1),
+                 "micv_fundamental_ls_host: bad flags %u, n %d, k %d, T %d or stride %d", flags, n, k, T, stride);
+    return geom_solve_host(ctx, s, "micv_fundamental_ls_host", ptsA, (size_t)n * 8, ptsB, (size_t)n * 8, n, indices,
+                           stride, k, T, 9, F, [&](float *a, float *b, int32_t *i, float *o, int32_t *st) {
+                               return micv_fundamental_ls_dev(ctx, a, b, n, i, stride, k, T, flags, o, st, s);
+                           });
+}
+
+int micv_fundamental_rank_reduce_host(micv_ctx *ctx, const float *F, int T, uint32_t flags, float *out) {
+    HOST_PROLOGUE("micv_fundamental_rank_reduce_host");
+    MICV_REQUIRE(F && out && T >= 1 && !(flags & ~MICV_GEOM_F64), "micv_fundamental_rank_reduce_host: bad argument");
+    DevBuf di((size_t)T * 36), dout((size_t)T * 36);
+    MICV_ALLOC_OK(di); MICV_ALLOC_OK(dout);
+    MICV_HIP(hipMemcpyAsync(di.p, F, (size_t)T * 36, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_fundamental_rank_reduce_dev(ctx, di.as<float>(), T, flags, dout.as<float>(), s));
+    MICV_HIP(hipMemcpyAsync(out, dout.p, (size_t)T * 36, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_fundamental_normalized_host(micv_ctx *ctx, const float *ptsA, const float *ptsB, int n, uint32_t flags,
+                                     float *Ta, float *Tb, float *Fhat, float *F) {
+    HOST_PROLOGUE("micv_fundamental_normalized_host");
+    MICV_REQUIRE(ptsA && ptsB && Ta && Tb && Fhat && F && n >= 1 && n <= 1 << 24 && !(flags & ~MICV_GEOM_F64),
+                 "micv_fundamental_normalized_host: bad argument");
+    DevBuf da((size_t)n * 8), db((size_t)n * 8), dout(4 * 36);
+    MICV_ALLOC_OK(da); MICV_ALLOC_OK(db); MICV_ALLOC_OK(dout);
+    MICV_HIP(hipMemcpyAsync(da.p, ptsA, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(db.p, ptsB, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    float *o = dout.as<float>();
+    MICV_TRY(micv_fundamental_normalized_dev(ctx, da.as<float>(), db.as<float>(), n, flags, o, o + 9, o + 18, o + 27, s));
+    MICV_HIP(hipMemcpyAsync(Ta, o, 36, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipMemcpyAsync(Tb, o + 9, 36, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipMemcpyAsync(Fhat, o + 18, 36, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipMemcpyAsync(F, o + 27, 36, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_epipolar_endpoints_host(micv_ctx *ctx, const float *F, const float *pts, int n, int side, int rows, int cols,
+                                 uint32_t flags, float *out) {
+    HOST_PROLOGUE("micv_epipolar_endpoints_host");
+    MICV_REQUIRE(F && pts && out && n >= 1 && n <= 1 << 28 && (side == 0 || side == 1) && rows >= 1 && cols >= 1 &&
+                     !(flags & ~MICV_GEOM_F64),
+                 "micv_epipolar_endpoints_host: bad argument");
+    DevBuf dF(36), dp((size_t)n * 8), dout((size_t)n * 24);
+    MICV_ALLOC_OK(dF); MICV_ALLOC_OK(dp); MICV_ALLOC_OK(dout);
+    MICV_HIP(hipMemcpyAsync(dF.p, F, 36, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(dp.p, pts, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_epipolar_endpoints_dev(ctx, dF.as<float>(), dp.as<float>(), n, side, rows, cols, flags,
+                                         dout.as<float>(), s));
+    MICV_HIP(hipMemcpyAsync(out, dout.p, (size_t)n * 24, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_camera_center_host(micv_ctx *ctx, const float *M, int T, uint32_t flags, float *center) {
+    HOST_PROLOGUE("micv_camera_center_host");
+    MICV_REQUIRE(M && center && T >= 1 && !(flags & ~MICV_GEOM_F64), "micv_camera_center_host: bad argument");
+    DevBuf dM((size_t)T * 48), dout((size_t)T * 12);
+    MICV_ALLOC_OK(dM); MICV_ALLOC_OK(dout);
+    MICV_HIP(hipMemcpyAsync(dM.p, M, (size_t)T * 48, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_camera_center_dev(ctx, dM.as<float>(), T, flags, dout.as<float>(), s));
+    MICV_HIP(hipMemcpyAsync(center, dout.p, (size_t)T * 12, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
 }  // extern "C"

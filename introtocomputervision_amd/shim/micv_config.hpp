@@ -8,6 +8,7 @@
 #include <cctype>
 #include <cstdlib>
 #include <fstream>
+#include <functional>
 #include <map>
 #include <memory>
 #include <ostream>
@@ -286,6 +287,54 @@ inline bool load_bbox(const std::string &filename, BBox &out) {
     out.x = v[0][0], out.y = v[0][1], out.width = v[1][0], out.height = v[1][1];
     return true;
 }
+
+// ps3's point files (ps3_cpp/include/FParse.h, lib/Config.cpp:20-30): one point per line, its coordinates separated
+// by whitespace; the matrix holds one point per COLUMN (a 2 x n or 3 x n row-major float array here: `dims` rows of
+// `n` floats).  False on a missing file, a token that is not a number, or lines of different lengths.
+struct PointSet {
+    int dims = 0, n = 0;
+    std::vector<float> data;  // [dims][n]
+};
+inline bool load_points(const std::string &filename, PointSet &out) {
+    std::ifstream input(filename);
+    if (!input.is_open()) return false;
+    std::vector<std::vector<float>> pts;
+    std::string line;
+    while (std::getline(input, line)) {
+        std::istringstream tokens(line);
+        std::vector<float> vals;
+        std::string tok;
+        while (tokens >> tok) {
+            char *end = nullptr;
+            const float f = std::strtof(tok.c_str(), &end);
+            if (end == tok.c_str() || *end) return false;
+            vals.push_back(f);
+        }
+        if (vals.empty()) continue;
+        if (!pts.empty() && vals.size() != pts[0].size()) return false;
+        pts.push_back(vals);
+    }
+    if (pts.empty()) return false;
+    out.dims = (int)pts[0].size();
+    out.n = (int)pts.size();
+    out.data.assign((size_t)out.dims * out.n, 0.f);
+    for (int i = 0; i < out.n; i++)
+        for (int d = 0; d < out.dims; d++) out.data[(size_t)d * out.n + i] = pts[i][d];
+    return true;
+}
+// Config::Points of ps3 (ps3_cpp/lib/Config.cpp:20-30): the five files of the `points:` section; `resolve` maps the
+// path the file names to the one to open (the reference opens it as written, relative to its working directory).
+struct PS3Points {
+    PointSet picA, picB, picANorm, pts3D, pts3DNorm;
+    bool ok = false;
+    explicit PS3Points(const Node &points,
+                       const std::function<std::string(const std::string &)> &resolve = [](const std::string &p) { return p; }) {
+        auto path = [&](const char *key) { return resolve(points.as<std::string>(key)); };
+        ok = load_points(path("pts2d_pic_a"), picA) && load_points(path("pts2d_pic_b"), picB) &&
+             load_points(path("pts2d_norm_pic_a"), picANorm) && load_points(path("pts3d"), pts3D) &&
+             load_points(path("pts3d_norm"), pts3DNorm);
+    }
+};
 
 // Config::MHI of ps7 (ps7_cpp/lib/Config.cpp:35-47); `last_frame` is in the file but never read there.
 struct MHI {

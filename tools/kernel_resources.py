@@ -42,7 +42,7 @@ def main():
         elif cur is not None:
             cur[k] = v
     for r in rows:
-        n = re.sub(r"\(.*", "", r["name"]).replace("void micv::", "")
+        n = re.sub(r"\(.*", "", r["name"].replace("(anonymous namespace)::", "")).replace("void micv::", "")
         if flt and flt not in n:
             continue
         print(f"{n:58s} vgpr {r.get('VGPRs','?'):>4} spill {r.get('VGPRs Spill','?'):>3} sgpr {r.get('TotalSGPRs','?'):>4} "
