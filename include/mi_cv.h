@@ -594,6 +594,69 @@ int micv_ransac_solve_matches_dev(micv_ctx *ctx, const float *kp_a, int64_t na, 
                                   double min_ratio, float *transforms, uint8_t *inlier_mask,
                                   int32_t *stats, micv_stream stream);
 
+/* -------------------------------------------------------- ps4: registration --------- */
+
+/* The tail of Solution::runProblem3 (ps4_cpp/src/Solution.cpp:315-325 for the similarity, :344-354 for the affine
+ * case): cv::invertAffineTransform(transform, transform), cv::warpAffine(simB, reverseWarp, transform, size) and
+ * blended = simA * 0.5 + reverseWarp * 0.5 (ps4-3-d, ps4-3-e).  Single-channel images of depth MICV_DEPTH_8U (the
+ * parity case: BasicConfig.h:61 reads the images 8-bit) or MICV_DEPTH_32F; strides in bytes; rows, cols <= 32767
+ * on both sides (cv::remap's int16 cell).  A 2x3 transform is six f32, row-major.  The `_dev` forms read it from
+ * DEVICE memory and never synchronise, so `transforms` of micv_ransac_solve_*_dev goes straight in (row [0] is what
+ * the reference returns).  OpenCV's source is not available to this repository: the arithmetic below is a decision
+ * of this library that restates OpenCV 3.4.1's imgwarp.cpp (unpinned; DESIGN.md section 2, "ps4 registration").
+ *
+ * cv::invertAffineTransform, all in double from the float entries, unfused, each result rounded once to float:
+ *   D = m0*m4 - m1*m3;  D = D != 0 ? 1/D : 0;  A11 = m4*D, A22 = m0*D, A12 = -m1*D, A21 = -m3*D;
+ *   b1 = -A11*m2 - A12*m5, b2 = -A21*m2 - A22*m5;  inv = {A11, A12, b1, A21, A22, b2}.
+ * `count` transforms, one lane each; count == 0 is a no-op. */
+int micv_invert_affine_dev(micv_ctx *ctx, const float *m, int count, float *inv, micv_stream stream);
+int micv_invert_affine_host(micv_ctx *ctx, const float *m, int count, float *inv);
+
+/* cv::warpAffine(src, dst, M, dsize, flags) with BORDER_CONSTANT 0.  flags = 0 is INTER_LINEAR with M mapping
+ * src -> dst (it is inverted again, in double); MICV_WARP_INVERSE_MAP uses M as the dst -> src map as given;
+ * MICV_WARP_NEAREST is INTER_NEAREST.  With cvRound = round half to even, INT_MIN for NaN or out of range, and
+ * int32 arithmetic that wraps:
+ *   X0(y) = cvRound((M1*y + M2)*1024) + d,  Y0(y) = cvRound((M4*y + M5)*1024) + d,
+ *   X = (X0 + cvRound(M0*x*1024)) >> s,     Y = (Y0 + cvRound(M3*x*1024)) >> s,    (d, s) = (16, 5) linear, (512, 10) nearest;
+ *   linear:  cell (sat16(X >> 5), sat16(Y >> 5)), fraction (X & 31, Y & 31) / 32; the four taps p00 p01 p10 p11, 0 outside;
+ *            u8:  (sum w*p + 16384) >> 15 with w = (32-fx)(32-fy)*32, fx(32-fy)*32, (32-fx)fy*32, fx*fy*32;
+ *            f32: p00*(ay0*ax0) + p01*(ay0*ax1) + p10*(ay1*ax0) + p11*(ay1*ax1), left to right, unfused -- the blend
+ *                 of micv_lk_warp (outside taps are 0.f and still multiplied: 0 * inf = NaN);
+ *   nearest: the pixel at (sat16(X), sat16(Y)), 0 outside.
+ * dst (drows x dcols) may differ in size from src; src == dst is an error.  One launch. */
+#define MICV_WARP_INVERSE_MAP 16 /* cv::WARP_INVERSE_MAP */
+#define MICV_WARP_NEAREST     1  /* INTER_NEAREST instead of INTER_LINEAR */
+int micv_warp_affine_dev(micv_ctx *ctx, const void *src, int depth, int srows, int scols, size_t sstride, const float *m,
+                         int flags, void *dst, int drows, int dcols, size_t dstride, micv_stream stream);
+int micv_warp_affine_host(micv_ctx *ctx, const void *src, int depth, int srows, int scols, size_t sstride, const float *m,
+                          int flags, void *dst, int drows, int dcols, size_t dstride);
+/* `count` warps in ONE launch: image i (src + i*src_pitch_bytes) by transform i (m + 6 i) into dst + i*dst_pitch_bytes
+ * -- a sequence registered to a key frame; src_pitch_bytes == 0 warps one shared source by `count` transforms.
+ * Same bits as `count` single calls.  count == 0 is a no-op. */
+int micv_warp_affine_batch_dev(micv_ctx *ctx, const void *src, size_t src_pitch_bytes, int depth, int srows, int scols,
+                               size_t sstride, const float *m, int count, int flags, void *dst, size_t dst_pitch_bytes,
+                               int drows, int dcols, size_t dstride, micv_stream stream);
+
+/* a * alpha + b * beta [+ gamma] on cv::Mat's = cv::addWeighted(a, alpha, b, beta, gamma): alpha, beta, gamma rounded to
+ * float, t = (a*alpha + b*beta) + gamma in float, unfused; f32 stores t, u8 stores cvRound(t) (ties to even) saturated to
+ * 0..255.  With alpha = beta = 0.5, gamma = 0 on u8 -- the only case the reference exercises (Solution.cpp:325,354) --
+ * every term is exact, so any evaluation order gives these bits.  dst may alias a or b. */
+int micv_add_weighted_dev(micv_ctx *ctx, const void *a, size_t astride, double alpha, const void *b, size_t bstride,
+                          double beta, double gamma, int depth, int rows, int cols, void *dst, size_t dstride,
+                          micv_stream stream);
+int micv_add_weighted_host(micv_ctx *ctx, const void *a, size_t astride, double alpha, const void *b, size_t bstride,
+                           double beta, double gamma, int depth, int rows, int cols, void *dst, size_t dstride);
+
+/* Solution.cpp:315-325 as ONE launch: m_a_to_b (what ransacHelper returns: it maps simA's points onto simB's) is
+ * inverted, b is warped back onto a (flags 0) and blended = a*0.5 + warped*0.5, the warped pixel staying in registers
+ * unless `warped` (optional, NULL = not wanted) asks for it.  Same bytes as micv_invert_affine + micv_warp_affine +
+ * micv_add_weighted.  a, b, warped, blended: rows x cols of `depth`. */
+int micv_register_blend_dev(micv_ctx *ctx, const void *a, size_t astride, const void *b, size_t bstride, int depth, int rows,
+                            int cols, const float *m_a_to_b, void *warped, size_t wstride, void *blended, size_t ostride,
+                            micv_stream stream);
+int micv_register_blend_host(micv_ctx *ctx, const void *a, size_t astride, const void *b, size_t bstride, int depth, int rows,
+                             int cols, const float *m_a_to_b, void *warped, size_t wstride, void *blended, size_t ostride);
+
 /* --------------------------------------------------- ps6: particle filter ---------- */
 
 /* ParticleFilter, ps6_cpp/include/ParticleFilter.h and lib/ParticleFilter.cpp, on the device: one tick is

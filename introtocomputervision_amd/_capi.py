@@ -38,6 +38,8 @@ MOMENTS_MAX_ORDERS, MOMENTS_MAX_ORDER = 16, 8
 KNN_F64_ACC = 1
 KNN_MAX_DIMS, KNN_MAX_K, KNN_MAX_LABELS, KNN_MAX_GROUPS = 64, 32, 16, 32
 GEOM_F64 = 1  # ps3 (mi_cv.h): geometry
+DEPTH_8U, DEPTH_32F = 0, 5  # mi_cv.h
+WARP_INVERSE_MAP, WARP_NEAREST = 16, 1  # ps4 registration (mi_cv.h)
 # micv_ctx_set_option (include/mi_cv.h): none of these changes a result
 (OPT_LK_STREAM_GROUPS, OPT_LK_FORCE_GENERIC, OPT_LK_NARROW_TILES, OPT_SOBEL_GENERIC, OPT_HARRIS_GENERIC,
  OPT_NMS_SCAN, OPT_STEREO_ROWS, OPT_LK_CHAIN, OPT_LK_SHORT_TILES, OPT_LK_STREAM, OPT_LK_TALL_TILES,
@@ -166,6 +168,16 @@ SIGNATURES = {
     "micv_ransac_solve_host": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, f64, vp, vp, vp]),
     "micv_ransac_solve_matches_dev": (i32, [vp, vp, i64, vp, i64, vp, vp, i64, C.c_uint64, i32, i32, i32, f64,
                                             vp, vp, vp, vp]),
+    # ps4 registration
+    "micv_invert_affine_dev": (i32, [vp, vp, i32, vp, vp]),
+    "micv_invert_affine_host": (i32, [vp, vp, i32, vp]),
+    "micv_warp_affine_dev": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, vp, i32, i32, sz, vp]),
+    "micv_warp_affine_host": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, vp, i32, i32, sz]),
+    "micv_warp_affine_batch_dev": (i32, [vp, vp, sz, i32, i32, i32, sz, vp, i32, i32, vp, sz, i32, i32, sz, vp]),
+    "micv_add_weighted_dev": (i32, [vp, vp, sz, f64, vp, sz, f64, f64, i32, i32, i32, vp, sz, vp]),
+    "micv_add_weighted_host": (i32, [vp, vp, sz, f64, vp, sz, f64, f64, i32, i32, i32, vp, sz]),
+    "micv_register_blend_dev": (i32, [vp, vp, sz, vp, sz, i32, i32, i32, vp, vp, sz, vp, sz, vp]),
+    "micv_register_blend_host": (i32, [vp, vp, sz, vp, sz, i32, i32, i32, vp, vp, sz, vp, sz]),
     # ps6 particle filter
     "micv_pf_create": (i32, [vp, vp, i32, i32, sz, i32, i32, i32, i32, i32, f64, f64, f32, f32, f64, u32,
                              C.c_uint64, C.POINTER(vp)]),

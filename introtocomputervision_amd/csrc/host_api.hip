@@ -1103,4 +1103,82 @@ int micv_camera_center_host(micv_ctx *ctx, const float *M, int T, uint32_t flags
     return MICV_OK;
 }
 
+// ps4 registration (warp.hip).  Sizes and strides are checked here as far as the copies need them (an image
+// of more than 32767 rows or columns is refused before anything is allocated); the `_dev` call checks the rest.
+static bool warp_image_ok(int depth, int rows, int cols, size_t stride) {
+    return (depth == MICV_DEPTH_8U || depth == MICV_DEPTH_32F) && rows > 0 && cols > 0 && rows <= 32767 &&
+           cols <= 32767 && stride_ok(stride, cols, depth == MICV_DEPTH_8U ? 1 : 4);
+}
+
+int micv_invert_affine_host(micv_ctx *ctx, const float *m, int count, float *inv) {
+    HOST_PROLOGUE("micv_invert_affine_host");
+    MICV_REQUIRE(m && inv && count >= 0, "micv_invert_affine_host: bad argument");
+    if (count == 0) return MICV_OK;
+    DevBuf dm((size_t)count * 24), di((size_t)count * 24);
+    MICV_ALLOC_OK(dm); MICV_ALLOC_OK(di);
+    MICV_HIP(hipMemcpyAsync(dm.p, m, (size_t)count * 24, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_invert_affine_dev(ctx, dm.as<float>(), count, di.as<float>(), s));
+    MICV_HIP(hipMemcpyAsync(inv, di.p, (size_t)count * 24, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_warp_affine_host(micv_ctx *ctx, const void *src, int depth, int srows, int scols, size_t sstride, const float *m,
+                          int flags, void *dst, int drows, int dcols, size_t dstride) {
+    HOST_PROLOGUE("micv_warp_affine_host");
+    MICV_REQUIRE(src && m && dst, "micv_warp_affine_host: null argument");
+    MICV_REQUIRE(warp_image_ok(depth, srows, scols, sstride) && warp_image_ok(depth, drows, dcols, dstride),
+                 "micv_warp_affine_host: bad depth %d, size %dx%d -> %dx%d (1..32767) or stride", depth, srows, scols, drows,
+                 dcols);
+    MICV_REQUIRE(src != dst, "micv_warp_affine_host: src and dst must not alias");
+    const size_t e = depth == MICV_DEPTH_8U ? 1 : 4, srb = (size_t)scols * e, drb = (size_t)dcols * e;
+    DevBuf ds(srb * srows), dd(drb * drows), dm(24);
+    MICV_ALLOC_OK(ds); MICV_ALLOC_OK(dd); MICV_ALLOC_OK(dm);
+    MICV_TRY(up2d(ds.p, src, sstride, srb, srows, s));
+    MICV_HIP(hipMemcpyAsync(dm.p, m, 24, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_warp_affine_dev(ctx, ds.p, depth, srows, scols, srb, dm.as<float>(), flags, dd.p, drows, dcols, drb, s));
+    MICV_TRY(down2d(dst, dstride, dd.p, drb, drows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_add_weighted_host(micv_ctx *ctx, const void *a, size_t astride, double alpha, const void *b, size_t bstride,
+                           double beta, double gamma, int depth, int rows, int cols, void *dst, size_t dstride) {
+    HOST_PROLOGUE("micv_add_weighted_host");
+    MICV_REQUIRE(a && b && dst, "micv_add_weighted_host: null argument");
+    MICV_REQUIRE(warp_image_ok(depth, rows, cols, astride) && warp_image_ok(depth, rows, cols, bstride) &&
+                     warp_image_ok(depth, rows, cols, dstride),
+                 "micv_add_weighted_host: bad depth %d, size %dx%d (1..32767) or stride", depth, rows, cols);
+    const size_t rb = (size_t)cols * (depth == MICV_DEPTH_8U ? 1 : 4), n = rb * rows;
+    DevBuf da(n), db(n), dd(n);
+    MICV_ALLOC_OK(da); MICV_ALLOC_OK(db); MICV_ALLOC_OK(dd);
+    MICV_TRY(up2d(da.p, a, astride, rb, rows, s));
+    MICV_TRY(up2d(db.p, b, bstride, rb, rows, s));
+    MICV_TRY(micv_add_weighted_dev(ctx, da.p, rb, alpha, db.p, rb, beta, gamma, depth, rows, cols, dd.p, rb, s));
+    MICV_TRY(down2d(dst, dstride, dd.p, rb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_register_blend_host(micv_ctx *ctx, const void *a, size_t astride, const void *b, size_t bstride, int depth, int rows,
+                             int cols, const float *m_a_to_b, void *warped, size_t wstride, void *blended, size_t ostride) {
+    HOST_PROLOGUE("micv_register_blend_host");
+    MICV_REQUIRE(a && b && m_a_to_b && blended, "micv_register_blend_host: null argument");
+    MICV_REQUIRE(warp_image_ok(depth, rows, cols, astride) && warp_image_ok(depth, rows, cols, bstride) &&
+                     warp_image_ok(depth, rows, cols, ostride) && (!warped || warp_image_ok(depth, rows, cols, wstride)),
+                 "micv_register_blend_host: bad depth %d, size %dx%d (1..32767) or stride", depth, rows, cols);
+    const size_t rb = (size_t)cols * (depth == MICV_DEPTH_8U ? 1 : 4), n = rb * rows;
+    DevBuf da(n), db(n), dw(warped ? n : 16), dd(n), dm(24);
+    MICV_ALLOC_OK(da); MICV_ALLOC_OK(db); MICV_ALLOC_OK(dw); MICV_ALLOC_OK(dd); MICV_ALLOC_OK(dm);
+    MICV_TRY(up2d(da.p, a, astride, rb, rows, s));
+    MICV_TRY(up2d(db.p, b, bstride, rb, rows, s));
+    MICV_HIP(hipMemcpyAsync(dm.p, m_a_to_b, 24, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_register_blend_dev(ctx, da.p, rb, db.p, rb, depth, rows, cols, dm.as<float>(), warped ? dw.p : nullptr, rb,
+                                     dd.p, rb, s));
+    if (warped) MICV_TRY(down2d(warped, wstride, dw.p, rb, rows, s));
+    MICV_TRY(down2d(blended, ostride, dd.p, rb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
 }  // extern "C"
