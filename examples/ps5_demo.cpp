@@ -2,6 +2,7 @@
 // as runProblem4 calls it :248-290) end to end on the shim, without OpenCV:
 //   ps5_demo <prev.ppm|pgm|bmp> <next...> <out_dir> [window = 15] [naive|pyr = pyr]
 //   ps5_demo --sequence <out_dir> <window> <frame0> <frame1> [<frame2> ...]   (all consecutive pairs, one library call)
+//   ps5_demo --sequence-device ...   the same, the colour maps of all pairs made on the device in one batch call
 // reads the two frames (colour or grey), runs lk::calcOpticalFlow / lk::calcOpticalFlowPyr through
 // libmicv.so, writes <out_dir>/flow.ppm (arrows), flow-uColorMap.ppm, flow-vColorMap.ppm, u.f32, v.f32
 // and pyramid.pgm (savePyramid of the previous frame's 4-level pyramid).
@@ -21,7 +22,8 @@ int main(int argc, char **argv) {
         return 2;
     }
     try {
-        if (std::string(argv[1]) == "--sequence") {
+        const bool device_maps = std::string(argv[1]) == "--sequence-device";
+        if (std::string(argv[1]) == "--sequence" || device_maps) {
             // ps5_demo --sequence <out_dir> <window> <frame0> <frame1> <frame2> ...: the flows of all consecutive pairs
             // (runProblem4's loop, Solution.cpp:255-285) through the frame-sequence entry; u<p>.f32 / v<p>.f32 per pair
             if (argc < 6) {
@@ -32,7 +34,8 @@ int main(int argc, char **argv) {
             const size_t win = (size_t)std::atoi(argv[3]);
             std::vector<micv_viz::Mat> frames;
             for (int i = 4; i < argc; i++) frames.push_back(micv_viz::imread(argv[i]));
-            const auto flows = micv_viz::denseLKSequence(frames, win, out, "flow");
+            const auto flows = device_maps ? micv_viz::denseLKSequenceDeviceMaps(frames, win, out, "flow")
+                                           : micv_viz::denseLKSequence(frames, win, out, "flow");
             for (size_t p = 0; p < flows.size(); p++)
                 for (int k = 0; k < 2; k++) {
                     const micv_viz::Mat &m = k ? flows[p].second : flows[p].first;

@@ -301,6 +301,7 @@ int micv_rgb8_to_gray_f32_dev(micv_ctx *ctx, const uint8_t *rgb, int rows, int c
  * accepts both; alpha is ignored), `depth` MICV_DEPTH_8U (fixed-point weights 4899/9617/1868 >> 14,
  * rounded) or MICV_DEPTH_32F ((c0*0.299f + c1*0.587f) + c2*0.114f, unfused).  sstride in bytes. */
 #define MICV_DEPTH_8U  0 /* CV_8U  */
+#define MICV_DEPTH_8S  1 /* CV_8S: the disparity maps; a source depth of the "display" block only */
 #define MICV_DEPTH_32F 5 /* CV_32F */
 int micv_to_gray_f32_dev(micv_ctx *ctx, const void *src, int rows, int cols, size_t sstride,
                          int channels, int depth, float *dst, size_t dstride, micv_stream stream);
@@ -656,6 +657,96 @@ int micv_register_blend_dev(micv_ctx *ctx, const void *a, size_t astride, const 
                             micv_stream stream);
 int micv_register_blend_host(micv_ctx *ctx, const void *a, size_t astride, const void *b, size_t bstride, int depth, int rows,
                              int cols, const float *m_a_to_b, void *warped, size_t wstride, void *blended, size_t ostride);
+
+/* ------------------------------------------------------------------ display -------- */
+
+/* The step that ends almost every runProblem* of the reference, on the device:
+ *   cv::normalize(x, x, 0, 255, cv::NORM_MINMAX, CV_8U)      ps2 main.cpp:94-320, ps4 Solution.cpp:67,108, ps5 :74-75,124
+ *   ones * 255 - x                                            ps2 main.cpp:126-127
+ *   cv::applyColorMap(x, x, cv::COLORMAP_JET)                 ps5 Solution.cpp:76-77
+ * and ps2's driver around it: addNoise (main.cpp:140-153), the contrast gain (:191-193), the left / right pair
+ * (:21-78).  OpenCV's source is not available to this repository: the arithmetic is a decision of this library that
+ * restates OpenCV 3.4's published behaviour (unpinned; DESIGN.md section 2, "display").
+ *
+ * Normalisation.  src is single-channel MICV_DEPTH_32F, MICV_DEPTH_8U or MICV_DEPTH_8S.  lo and hi are the minimum and
+ * maximum of the image as floats, NaNs skipped, +/-Inf taking part; then, in double and unfused,
+ *   scale = 255.0 * (hi - lo > DBL_EPSILON ? 1.0 / (hi - lo) : 0.0),  shift = 0.0 - lo * scale,
+ *   a = (float)scale, b = (float)shift,  t = (float)src * a + b   (float, unfused),
+ *   dst = isfinite(t) ? clamp(rint(t), 0, 255) : 0                (ties to even).
+ * An image without a single non-NaN value gives a = b = 0 (all zeros).  One pass writes up to three images, each
+ * optional (NULL), at least one wanted: dst_u8 (1 byte per pixel), dst_inverted = 255 - dst and dst_jet = the JET
+ * colour of dst, 3 bytes per pixel B, G, R.  The JET table is entry i = cvRound(255 * clamp(1.5 - |4 x - k|, 0, 1)),
+ * k = 1 (B), 2 (G), 3 (R), x = i / 255.0 in double, built once per context on the host.  minmax_out (optional, DEVICE,
+ * 2 floats per image) receives lo and hi (NaN, NaN for an image of NaNs).  Strides in bytes; rows * cols < 2^31.
+ * Two launches (min / max, apply) however many images; lo and hi are exact, so nothing depends on the grid.  A context
+ * keeps the min / max words of the running call: it serves one stream at a time, like its scratch arena. */
+int micv_normalize_minmax_dev(micv_ctx *ctx, const void *src, int depth, int rows, int cols, size_t sstride,
+                              uint8_t *dst_u8, size_t u8_stride, uint8_t *dst_inverted, size_t inverted_stride,
+                              uint8_t *dst_jet, size_t jet_stride, float *minmax_out, micv_stream stream);
+int micv_normalize_minmax_host(micv_ctx *ctx, const void *src, int depth, int rows, int cols, size_t sstride,
+                               uint8_t *dst_u8, size_t u8_stride, uint8_t *dst_inverted, size_t inverted_stride,
+                               uint8_t *dst_jet, size_t jet_stride, float *minmax_out);
+/* `batch` images of one shape, image i at base + i * pitch (bytes) on every side, each normalised by its own range: the
+ * same bytes as `batch` single calls, in two launches.  batch == 0 is a no-op.  (minmax_out of the _host form is host
+ * memory, as all its pointers are.) */
+int micv_normalize_minmax_batch_dev(micv_ctx *ctx, const void *src, size_t src_pitch, int depth, int batch, int rows, int cols,
+                                    size_t sstride, uint8_t *dst_u8, size_t u8_pitch, size_t u8_stride,
+                                    uint8_t *dst_inverted, size_t inverted_pitch, size_t inverted_stride, uint8_t *dst_jet,
+                                    size_t jet_pitch, size_t jet_stride, float *minmax_out, micv_stream stream);
+int micv_normalize_minmax_batch_host(micv_ctx *ctx, const void *src, size_t src_pitch, int depth, int batch, int rows, int cols,
+                                     size_t sstride, uint8_t *dst_u8, size_t u8_pitch, size_t u8_stride,
+                                     uint8_t *dst_inverted, size_t inverted_pitch, size_t inverted_stride, uint8_t *dst_jet,
+                                     size_t jet_pitch, size_t jet_stride, float *minmax_out);
+
+/* cv::applyColorMap(src, dst, cv::COLORMAP_JET) alone: CV_8UC1 -> CV_8UC3 (B, G, R) through the same table. */
+int micv_apply_colormap_jet_dev(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, uint8_t *dst_jet,
+                                size_t jet_stride, micv_stream stream);
+int micv_apply_colormap_jet_host(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, uint8_t *dst_jet,
+                                 size_t jet_stride);
+
+/* dst = src * gain + (noise ? noise : 0.f) in float, unfused.  gain = 1: `first + noise` (main.cpp:148) bit for bit;
+ * noise = NULL: `left * contrastFactor` (main.cpp:192: convertTo with a float scale and a float zero shift).  dst may
+ * alias src. */
+int micv_gain_noise_f32_dev(micv_ctx *ctx, const float *src, size_t sstride, float gain, const float *noise, size_t nstride,
+                            int rows, int cols, float *dst, size_t dstride, micv_stream stream);
+int micv_gain_noise_f32_host(micv_ctx *ctx, const float *src, size_t sstride, float gain, const float *noise, size_t nstride,
+                             int rows, int cols, float *dst, size_t dstride);
+
+/* cv::randn(dst, mean, sigma) on a CV_32FC1 image from a cv::RNG whose 64-bit state is *state (cv::theRNG() starts at
+ * 0xffffffff; 0 is taken as that): sample i in row-major order is the i-th ziggurat draw z of the generator (the one
+ * micv_pf_create draws its tables from), stored as z * sigma + mean in float, unfused.  *state comes back advanced, so
+ * consecutive calls continue one generator.  Host memory, host code: the ziggurat takes a data-dependent number of
+ * words from a serial generator. */
+int micv_cv_randn_f32_host(uint64_t *state, float mean, float sigma, int rows, int cols, float *dst, size_t dstride);
+
+/* disparitySSDPair / disparityNCorrPair (main.cpp:21-78): disp_left = search(left, right) over [-disparity_range, 0],
+ * disp_right = search(right, left) over [0, disparity_range]; the bytes of the two micv_disparity_* calls, which are
+ * what it issues on `stream`.  flags as there; disparity_range 0..127. */
+#define MICV_DISPARITY_SSD 0
+#define MICV_DISPARITY_NCC 1
+int micv_disparity_pair_dev(micv_ctx *ctx, const float *left, const float *right, int rows, int cols, size_t stride,
+                            int window_rad, int disparity_range, int metric, int flags, int8_t *disp_left,
+                            int8_t *disp_right, size_t dstride, micv_stream stream);
+int micv_disparity_pair_host(micv_ctx *ctx, const float *left, const float *right, int rows, int cols, size_t stride,
+                             int window_rad, int disparity_range, int metric, int flags, int8_t *disp_left,
+                             int8_t *disp_right, size_t dstride);
+/* One pair-and-display block of a runProblem* after the grey conversion, on one stream without a host synchronise:
+ * left' = left * gain + noise_left, right' = right * gain + noise_right (gain 1.f and both noise images NULL: the
+ * images as they are; the noise images come together or not at all), the pair on left', right', then the images the
+ * driver writes: image_left = normalised disp_left, image_left_inverted = 255 - image_left (optional), image_right =
+ * normalised disp_right.  The maps come back too.  `work` (device, 2 * rows * cols floats) holds left' and right'
+ * and is needed only with a gain other than 1.f or with noise.  The _host form uploads left, right (and the noise images) and
+ * downloads the two maps and the 8-bit images, nothing else. */
+int micv_disparity_pair_display_dev(micv_ctx *ctx, const float *left, const float *right, int rows, int cols, size_t stride,
+                                    float gain, const float *noise_left, const float *noise_right, size_t nstride,
+                                    int window_rad, int disparity_range, int metric, int flags, int8_t *disp_left,
+                                    int8_t *disp_right, size_t dstride, uint8_t *image_left, uint8_t *image_left_inverted,
+                                    uint8_t *image_right, size_t istride, float *work, micv_stream stream);
+int micv_disparity_pair_display_host(micv_ctx *ctx, const float *left, const float *right, int rows, int cols, size_t stride,
+                                     float gain, const float *noise_left, const float *noise_right, size_t nstride,
+                                     int window_rad, int disparity_range, int metric, int flags, int8_t *disp_left,
+                                     int8_t *disp_right, size_t dstride, uint8_t *image_left, uint8_t *image_left_inverted,
+                                     uint8_t *image_right, size_t istride);
 
 /* --------------------------------------------------- ps6: particle filter ---------- */
 

@@ -38,7 +38,8 @@ MOMENTS_MAX_ORDERS, MOMENTS_MAX_ORDER = 16, 8
 KNN_F64_ACC = 1
 KNN_MAX_DIMS, KNN_MAX_K, KNN_MAX_LABELS, KNN_MAX_GROUPS = 64, 32, 16, 32
 GEOM_F64 = 1  # ps3 (mi_cv.h): geometry
-DEPTH_8U, DEPTH_32F = 0, 5  # mi_cv.h
+DEPTH_8U, DEPTH_8S, DEPTH_32F = 0, 1, 5  # mi_cv.h
+DISPARITY_SSD, DISPARITY_NCC = 0, 1  # display (mi_cv.h)
 WARP_INVERSE_MAP, WARP_NEAREST = 16, 1  # ps4 registration (mi_cv.h)
 # micv_ctx_set_option (include/mi_cv.h): none of these changes a result
 (OPT_LK_STREAM_GROUPS, OPT_LK_FORCE_GENERIC, OPT_LK_NARROW_TILES, OPT_SOBEL_GENERIC, OPT_HARRIS_GENERIC,
@@ -178,6 +179,22 @@ SIGNATURES = {
     "micv_add_weighted_host": (i32, [vp, vp, sz, f64, vp, sz, f64, f64, i32, i32, i32, vp, sz]),
     "micv_register_blend_dev": (i32, [vp, vp, sz, vp, sz, i32, i32, i32, vp, vp, sz, vp, sz, vp]),
     "micv_register_blend_host": (i32, [vp, vp, sz, vp, sz, i32, i32, i32, vp, vp, sz, vp, sz]),
+    # display
+    "micv_normalize_minmax_dev": (i32, [vp, vp, i32, i32, i32, sz, vp, sz, vp, sz, vp, sz, vp, vp]),
+    "micv_normalize_minmax_host": (i32, [vp, vp, i32, i32, i32, sz, vp, sz, vp, sz, vp, sz, vp]),
+    "micv_normalize_minmax_batch_dev": (i32, [vp, vp, sz, i32, i32, i32, i32, sz, vp, sz, sz, vp, sz, sz, vp, sz, sz, vp, vp]),
+    "micv_normalize_minmax_batch_host": (i32, [vp, vp, sz, i32, i32, i32, i32, sz, vp, sz, sz, vp, sz, sz, vp, sz, sz, vp]),
+    "micv_apply_colormap_jet_dev": (i32, [vp, vp, i32, i32, sz, vp, sz, vp]),
+    "micv_apply_colormap_jet_host": (i32, [vp, vp, i32, i32, sz, vp, sz]),
+    "micv_gain_noise_f32_dev": (i32, [vp, vp, sz, f32, vp, sz, i32, i32, vp, sz, vp]),
+    "micv_gain_noise_f32_host": (i32, [vp, vp, sz, f32, vp, sz, i32, i32, vp, sz]),
+    "micv_cv_randn_f32_host": (i32, [C.POINTER(C.c_uint64), f32, f32, i32, i32, vp, sz]),
+    "micv_disparity_pair_dev": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "micv_disparity_pair_host": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, vp, vp, sz]),
+    "micv_disparity_pair_display_dev": (i32, [vp, vp, vp, i32, i32, sz, f32, vp, vp, sz, i32, i32, i32, i32, vp, vp, sz, vp, vp,
+                                              vp, sz, vp, vp]),
+    "micv_disparity_pair_display_host": (i32, [vp, vp, vp, i32, i32, sz, f32, vp, vp, sz, i32, i32, i32, i32, vp, vp, sz, vp, vp,
+                                               vp, sz]),
     # ps6 particle filter
     "micv_pf_create": (i32, [vp, vp, i32, i32, sz, i32, i32, i32, i32, i32, f64, f64, f32, f32, f64, u32,
                              C.c_uint64, C.POINTER(vp)]),

@@ -82,6 +82,8 @@ __host__ __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? l
 
 // Host: cv::getGaussianKernel(n, sigma, CV_32F) for sigma > 0.
 void gaussian_taps(int n, double sigma, Taps *out);
+// Host: the JET table of display.hip, entry i = B | G << 8 | R << 16.
+void jet_lut_packed(unsigned *lut256);
 // Host: cv::getDerivKernels integer taps for one direction; returns tap count or -1.
 int sobel_taps(int ksize, int order, Taps *out);
 
@@ -138,6 +140,12 @@ struct micv_ctx {
     unsigned *stereo_flag = nullptr;
     unsigned stereo_epoch = 0;
     int stereo_flag_word(unsigned **out);
+    // display.hip: 256 packed JET entries (B | G << 8 | R << 16), then for every image of a batch chunk kDisplayKeySlots
+    // pairs of min / max key words, each pair in a 128-byte line of its own (reset on the stream by every call).
+    // Allocated and filled with the context, so that no `_dev` call allocates.
+    static constexpr int kDisplayMaxBatch = 1024, kDisplayKeySlots = 16, kDisplayKeyStride = 32;
+    static constexpr size_t kDisplayStateBytes = 1024 + (size_t)kDisplayMaxBatch * kDisplayKeySlots * kDisplayKeyStride * 4;
+    void *display_state = nullptr;
     int cu_count = 0;  // multiProcessorCount, read once
     int wave_slots(int waves_per_simd);
     // Hough trig tables (hough.hip), uploaded once per context: [0] theta = -90.., [1] theta = 0..

@@ -219,6 +219,17 @@ int micv_ctx_create(int device, micv_ctx **out) {
         delete c;
         return MICV_EHIP;
     }
+    unsigned lut[256];
+    micv::jet_lut_packed(lut);
+    e = hipMalloc(&c->display_state, micv_ctx::kDisplayStateBytes);
+    if (e == hipSuccess) e = hipMemcpy(c->display_state, lut, sizeof(lut), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        micv::set_error("micv_ctx_create: display state: %s", hipGetErrorString(e));
+        if (c->display_state) (void)hipFree(c->display_state);
+        (void)hipHostFree(c->pinned);
+        delete c;
+        return e == hipErrorOutOfMemory ? MICV_ENOMEM : MICV_EHIP;
+    }
     *out = c;
     return MICV_OK;
 }
@@ -238,6 +249,7 @@ void micv_ctx_destroy(micv_ctx *ctx) {
     for (auto &e : ctx->lk_sched) (void)hipFree(e.dev);
     if (ctx->lk_tickets) (void)hipFree(ctx->lk_tickets);
     if (ctx->stereo_flag) (void)hipFree(ctx->stereo_flag);
+    if (ctx->display_state) (void)hipFree(ctx->display_state);
     for (auto &c : ctx->compact_slots)
         if (c.buf) (void)hipFree(c.buf);
     for (void *t : ctx->trig_tables)

@@ -1181,4 +1181,148 @@ int micv_register_blend_host(micv_ctx *ctx, const void *a, size_t astride, const
     return MICV_OK;
 }
 
+// display (display.hip).  Device images are packed (row = cols elements) at 256-byte-aligned pitches.
+static bool display_src_ok(int depth, int rows, int cols, size_t stride) {
+    return (depth == MICV_DEPTH_32F || depth == MICV_DEPTH_8U || depth == MICV_DEPTH_8S) && rows > 0 && cols > 0 &&
+           (int64_t)rows * cols < ((int64_t)1 << 31) && stride_ok(stride, cols, depth == MICV_DEPTH_32F ? 4 : 1);
+}
+static size_t pitch256(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+
+int micv_normalize_minmax_batch_host(micv_ctx *ctx, const void *src, size_t src_pitch, int depth, int batch, int rows, int cols,
+                                     size_t sstride, uint8_t *dst_u8, size_t u8_pitch, size_t u8_stride,
+                                     uint8_t *dst_inverted, size_t inverted_pitch, size_t inverted_stride, uint8_t *dst_jet,
+                                     size_t jet_pitch, size_t jet_stride, float *minmax_out) {
+    HOST_PROLOGUE("micv_normalize_minmax_host");
+    MICV_REQUIRE(src && (dst_u8 || dst_inverted || dst_jet), "micv_normalize_minmax_host: no source or no output wanted");
+    MICV_REQUIRE(batch >= 0 && display_src_ok(depth, rows, cols, sstride),
+                 "micv_normalize_minmax_host: bad batch %d, depth %d, size %dx%d (rows * cols < 2^31) or stride", batch, depth, rows, cols);
+    MICV_REQUIRE((!dst_u8 || u8_stride >= (size_t)cols) && (!dst_inverted || inverted_stride >= (size_t)cols) &&
+                     (!dst_jet || jet_stride >= 3 * (size_t)cols),
+                 "micv_normalize_minmax_host: an output's stride is smaller than its rows");
+    const size_t last = (size_t)(rows - 1);
+    MICV_REQUIRE(batch <= 1 || (src_pitch >= last * sstride + (size_t)cols * (depth == MICV_DEPTH_32F ? 4 : 1) &&
+                                (!dst_u8 || u8_pitch >= last * u8_stride + (size_t)cols) &&
+                                (!dst_inverted || inverted_pitch >= last * inverted_stride + (size_t)cols) &&
+                                (!dst_jet || jet_pitch >= last * jet_stride + 3 * (size_t)cols)),
+                 "micv_normalize_minmax_host: a pitch is smaller than an image");
+    if (batch == 0) return MICV_OK;
+    const size_t e = depth == MICV_DEPTH_32F ? 4 : 1, srb = (size_t)cols * e, sp = pitch256(srb * rows);
+    const size_t gp = pitch256((size_t)cols * rows), jp = pitch256(3 * (size_t)cols * rows), nb = (size_t)batch;
+    DevBuf ds(sp * nb), du(dst_u8 ? gp * nb : 16), di(dst_inverted ? gp * nb : 16), dj(dst_jet ? jp * nb : 16), dm(8 * nb);
+    MICV_ALLOC_OK(ds); MICV_ALLOC_OK(du); MICV_ALLOC_OK(di); MICV_ALLOC_OK(dj); MICV_ALLOC_OK(dm);
+    for (size_t i = 0; i < nb; i++)
+        MICV_TRY(up2d(ds.as<char>() + i * sp, static_cast<const char *>(src) + i * src_pitch, sstride, srb, rows, s));
+    MICV_TRY(micv_normalize_minmax_batch_dev(ctx, ds.p, sp, depth, batch, rows, cols, srb, dst_u8 ? du.as<uint8_t>() : nullptr, gp,
+                                             (size_t)cols, dst_inverted ? di.as<uint8_t>() : nullptr, gp, (size_t)cols,
+                                             dst_jet ? dj.as<uint8_t>() : nullptr, jp, 3 * (size_t)cols, dm.as<float>(), s));
+    for (size_t i = 0; i < nb; i++) {
+        if (dst_u8) MICV_TRY(down2d(dst_u8 + i * u8_pitch, u8_stride, du.as<char>() + i * gp, (size_t)cols, rows, s));
+        if (dst_inverted) MICV_TRY(down2d(dst_inverted + i * inverted_pitch, inverted_stride, di.as<char>() + i * gp, (size_t)cols, rows, s));
+        if (dst_jet) MICV_TRY(down2d(dst_jet + i * jet_pitch, jet_stride, dj.as<char>() + i * jp, 3 * (size_t)cols, rows, s));
+    }
+    if (minmax_out) MICV_HIP(hipMemcpyAsync(minmax_out, dm.p, 8 * nb, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_normalize_minmax_host(micv_ctx *ctx, const void *src, int depth, int rows, int cols, size_t sstride,
+                               uint8_t *dst_u8, size_t u8_stride, uint8_t *dst_inverted, size_t inverted_stride,
+                               uint8_t *dst_jet, size_t jet_stride, float *minmax_out) {
+    return micv_normalize_minmax_batch_host(ctx, src, 0, depth, 1, rows, cols, sstride, dst_u8, 0, u8_stride, dst_inverted, 0,
+                                            inverted_stride, dst_jet, 0, jet_stride, minmax_out);
+}
+
+int micv_apply_colormap_jet_host(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, uint8_t *dst_jet,
+                                 size_t jet_stride) {
+    HOST_PROLOGUE("micv_apply_colormap_jet_host");
+    MICV_REQUIRE(src && dst_jet && display_src_ok(MICV_DEPTH_8U, rows, cols, sstride) && jet_stride >= 3 * (size_t)cols,
+                 "micv_apply_colormap_jet_host: bad argument, size %dx%d (rows * cols < 2^31) or stride", rows, cols);
+    const size_t n = (size_t)rows * cols;
+    DevBuf ds(n), dj(3 * n);
+    MICV_ALLOC_OK(ds); MICV_ALLOC_OK(dj);
+    MICV_TRY(up2d(ds.p, src, sstride, (size_t)cols, rows, s));
+    MICV_TRY(micv_apply_colormap_jet_dev(ctx, ds.as<uint8_t>(), rows, cols, (size_t)cols, dj.as<uint8_t>(), 3 * (size_t)cols, s));
+    MICV_TRY(down2d(dst_jet, jet_stride, dj.p, 3 * (size_t)cols, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_gain_noise_f32_host(micv_ctx *ctx, const float *src, size_t sstride, float gain, const float *noise, size_t nstride,
+                             int rows, int cols, float *dst, size_t dstride) {
+    HOST_PROLOGUE("micv_gain_noise_f32_host");
+    MICV_REQUIRE(src && dst && rows > 0 && cols > 0 && stride_ok(sstride, cols, 4) && stride_ok(dstride, cols, 4) &&
+                     (!noise || stride_ok(nstride, cols, 4)),
+                 "micv_gain_noise_f32_host: bad argument, size %dx%d or stride", rows, cols);
+    const size_t rb = (size_t)cols * 4, n = rb * rows;
+    DevBuf ds(n), dn(noise ? n : 16);
+    MICV_ALLOC_OK(ds); MICV_ALLOC_OK(dn);
+    MICV_TRY(up2d(ds.p, src, sstride, rb, rows, s));
+    if (noise) MICV_TRY(up2d(dn.p, noise, nstride, rb, rows, s));
+    MICV_TRY(micv_gain_noise_f32_dev(ctx, ds.as<float>(), rb, gain, noise ? dn.as<float>() : nullptr, rb, rows, cols, ds.as<float>(),
+                                     rb, s));
+    MICV_TRY(down2d(dst, dstride, ds.p, rb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+// One body for the pair with and without its display images (img_left == nullptr: the maps alone).
+static int pair_host(const char *fn, micv_ctx *ctx, const float *left, const float *right, int rows, int cols, size_t stride,
+                     float gain, const float *noise_left, const float *noise_right, size_t nstride, int rad, int range,
+                     int metric, int flags, int8_t *disp_left, int8_t *disp_right, size_t dstride, bool display,
+                     uint8_t *img_left, uint8_t *img_left_inv, uint8_t *img_right, size_t istride) {
+    HOST_PROLOGUE("micv_disparity_pair_host");
+    MICV_REQUIRE(left && right && disp_left && disp_right && (!display || (img_left && img_right)), "%s: null argument", fn);
+    MICV_REQUIRE(rows > 0 && cols > 0 && (int64_t)rows * cols < ((int64_t)1 << 31) && stride_ok(stride, cols, 4) &&
+                     dstride >= (size_t)cols && (!display || istride >= (size_t)cols),
+                 "%s: bad size %dx%d (rows * cols < 2^31) or stride", fn, rows, cols);
+    MICV_REQUIRE(!noise_left == !noise_right && (!noise_left || stride_ok(nstride, cols, 4)),
+                 "%s: one noise image without the other, or a bad noise stride", fn);
+    const size_t rb = (size_t)cols * 4, n = rb * rows, g = pitch256((size_t)cols * rows);
+    const bool change = noise_left || gain != 1.f;
+    DevBuf dl(n), dr(n), dnl(noise_left ? n : 16), dnr(noise_left ? n : 16), dw(change ? 2 * n : 16), dd(2 * g), di(display ? 3 * g : 16);
+    MICV_ALLOC_OK(dl); MICV_ALLOC_OK(dr); MICV_ALLOC_OK(dnl); MICV_ALLOC_OK(dnr); MICV_ALLOC_OK(dw); MICV_ALLOC_OK(dd); MICV_ALLOC_OK(di);
+    MICV_TRY(up2d(dl.p, left, stride, rb, rows, s));
+    MICV_TRY(up2d(dr.p, right, stride, rb, rows, s));
+    if (noise_left) {
+        MICV_TRY(up2d(dnl.p, noise_left, nstride, rb, rows, s));
+        MICV_TRY(up2d(dnr.p, noise_right, nstride, rb, rows, s));
+    }
+    int8_t *d0 = dd.as<int8_t>(), *d1 = d0 + g;
+    uint8_t *i0 = di.as<uint8_t>(), *i1 = i0 + g, *i2 = i1 + g;
+    if (display)
+        MICV_TRY(micv_disparity_pair_display_dev(ctx, dl.as<float>(), dr.as<float>(), rows, cols, rb, gain,
+                                                 noise_left ? dnl.as<float>() : nullptr, noise_left ? dnr.as<float>() : nullptr, rb,
+                                                 rad, range, metric, flags, d0, d1, (size_t)cols, i0, img_left_inv ? i1 : nullptr, i2,
+                                                 (size_t)cols, change ? dw.as<float>() : nullptr, s));
+    else
+        MICV_TRY(micv_disparity_pair_dev(ctx, dl.as<float>(), dr.as<float>(), rows, cols, rb, rad, range, metric, flags, d0, d1,
+                                         (size_t)cols, s));
+    MICV_TRY(down2d(disp_left, dstride, d0, (size_t)cols, rows, s));
+    MICV_TRY(down2d(disp_right, dstride, d1, (size_t)cols, rows, s));
+    if (display) {
+        MICV_TRY(down2d(img_left, istride, i0, (size_t)cols, rows, s));
+        if (img_left_inv) MICV_TRY(down2d(img_left_inv, istride, i1, (size_t)cols, rows, s));
+        MICV_TRY(down2d(img_right, istride, i2, (size_t)cols, rows, s));
+    }
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_disparity_pair_host(micv_ctx *ctx, const float *left, const float *right, int rows, int cols, size_t stride,
+                             int window_rad, int disparity_range, int metric, int flags, int8_t *disp_left,
+                             int8_t *disp_right, size_t dstride) {
+    return pair_host("micv_disparity_pair_host", ctx, left, right, rows, cols, stride, 1.f, nullptr, nullptr, 0, window_rad,
+                     disparity_range, metric, flags, disp_left, disp_right, dstride, false, nullptr, nullptr, nullptr, 0);
+}
+
+int micv_disparity_pair_display_host(micv_ctx *ctx, const float *left, const float *right, int rows, int cols, size_t stride,
+                                     float gain, const float *noise_left, const float *noise_right, size_t nstride,
+                                     int window_rad, int disparity_range, int metric, int flags, int8_t *disp_left,
+                                     int8_t *disp_right, size_t dstride, uint8_t *image_left, uint8_t *image_left_inverted,
+                                     uint8_t *image_right, size_t istride) {
+    return pair_host("micv_disparity_pair_display_host", ctx, left, right, rows, cols, stride, gain, noise_left, noise_right, nstride,
+                     window_rad, disparity_range, metric, flags, disp_left, disp_right, dstride, true, image_left,
+                     image_left_inverted, image_right, istride);
+}
+
 }  // extern "C"

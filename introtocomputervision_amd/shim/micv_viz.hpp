@@ -358,6 +358,50 @@ inline std::vector<std::pair<Mat, Mat>> denseLKSequence(const std::vector<Mat> &
     return out;
 }
 
+// denseLKSequence with the colour maps made on the device: the 2 * pairs flow fields go through ONE call of the batch
+// entry (micv_normalize_minmax_batch_host: each field by its own range, two launches, only the B, G, R images come back)
+// instead of normalize_minmax_u8 + apply_colormap_jet on one host thread.  Same files, same bytes.
+inline std::vector<std::pair<Mat, Mat>> denseLKSequenceDeviceMaps(const std::vector<Mat> &frames, const size_t windowSize,
+                                                                  const std::string &filePrefix, const std::string &outputImg,
+                                                                  bool saveColorMaps = true, const std::string &ext = ".ppm") {
+    std::vector<Mat> u, v;
+    lk::calcOpticalFlowPyrSequence(frames, u, v, windowSize);
+    std::vector<Mat> maps;
+    if (saveColorMaps && !u.empty()) {
+        const int rows = u[0].rows, cols = u[0].cols;
+        const size_t n = (size_t)rows * cols;
+        std::vector<float> fields(2 * u.size() * n);  // u0 v0 u1 v1 ...: the batch entry takes one base and a pitch
+        for (size_t p = 0; p < u.size(); p++)
+            for (int k = 0; k < 2; k++) {
+                const Mat &f = k ? v[p] : u[p];
+                micv_shim::require(f.type() == micv_shim::F32 && f.rows == rows && f.cols == cols, "denseLKSequence: flow fields of one size expected");
+                for (int y = 0; y < rows; y++) std::memcpy(&fields[(2 * p + k) * n + (size_t)y * cols], f.ptr<float>(y), (size_t)cols * 4);
+            }
+        std::vector<unsigned char> jet(2 * u.size() * n * 3);
+        micv_shim::check(micv_normalize_minmax_batch_host(micv_shim::context(), fields.data(), n * 4, MICV_DEPTH_32F, (int)(2 * u.size()),
+                                                          rows, cols, (size_t)cols * 4, nullptr, 0, 0, nullptr, 0, 0, jet.data(), n * 3,
+                                                          (size_t)cols * 3, nullptr));
+        for (size_t i = 0; i < 2 * u.size(); i++) {
+            Mat m(rows, cols, micv::CV_8UC3);
+            for (int y = 0; y < rows; y++) std::memcpy(m.ptr<unsigned char>(y), &jet[i * n * 3 + (size_t)y * cols * 3], (size_t)cols * 3);
+            maps.push_back(m);
+        }
+    }
+    std::vector<std::pair<Mat, Mat>> out;
+    for (size_t p = 0; p < u.size(); p++) {
+        const std::string name = outputImg + std::to_string(p);
+        Mat velocityVectors = frames[p].clone();
+        drawVelocityVectors(velocityVectors, u[p], v[p], Scalar(0, 255, 0, 255));
+        imwrite(filePrefix + "/" + name + ext, velocityVectors);
+        if (saveColorMaps) {
+            imwrite(filePrefix + "/" + name + "-uColorMap" + ext, maps[2 * p]);
+            imwrite(filePrefix + "/" + name + "-vColorMap" + ext, maps[2 * p + 1]);
+        }
+        out.emplace_back(u[p], v[p]);
+    }
+    return out;
+}
+
 // cv::resize(src, dst, size, fx, fy, INTER_NEAREST) for an integer up-scale factor k.
 inline Mat resize_nearest(const Mat &src, int rows, int cols) {
     Mat dst(rows, cols, src.type());
