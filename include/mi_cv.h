@@ -362,6 +362,8 @@ int micv_harris_response_ex_host(micv_ctx *ctx, const float *gx, const float *gy
 /* harris::{cpu,gpu}::refineCorners, Harris.cpp:99-147 / Harris.cu:243-329 (a10).
  * corners: rows x cols f32, zero except kept maxima.  locs_yx: capacity `cap` (y,x) int32
  * pairs, filled in row-major order; *count receives the number found (may exceed cap).
+ * The list follows Harris.cpp: every kept pixel, whatever its value (Harris.cu:301-306 lists only map entries > 0 and so
+ * drops kept corners of value <= 0 when the threshold is <= 0).  min_distance 0 keeps every pixel >= threshold.
  * The _dev flavour leaves count/locs in device memory. */
 int micv_harris_refine_dev(micv_ctx *ctx, const float *resp, int rows, int cols, size_t rstride,
                            double threshold, int min_distance, float *corners, size_t cstride,
@@ -512,14 +514,16 @@ int micv_generate_edge_host(micv_ctx *ctx, const uint8_t *src, int rows, int col
 /* cv::BFMatcher::create()->knnMatch(query, train, matches, 2), ps4_cpp/src/Solution.cpp:172-179:
  * NORM_L2, no cross-check.  query is nq x dim, train nt x dim (f32, strides in bytes, nt >= 2).
  * idx2 [nq][2] = train indices of the nearest and second nearest, dist2 [nq][2] their distances,
- * ordered by (distance, index). */
+ * ordered by (distance, index).  +inf is a distance like any other.  A NaN distance is never selected: with fewer than
+ * two non-NaN distances the empty places hold index -1 and distance +inf (an all-NaN train set: both). */
 int micv_bf_knn2_dev(micv_ctx *ctx, const float *query, int nq, size_t qstride, const float *train,
                      int nt, size_t tstride, int dim, int32_t *idx2, float *dist2,
                      micv_stream stream);
 int micv_bf_knn2_host(micv_ctx *ctx, const float *query, int nq, size_t qstride, const float *train,
                       int nt, size_t tstride, int dim, int32_t *idx2, float *dist2);
 /* The ratio test of Solution.cpp:180-184: keep query q when dist0 < ratio * dist1.  matches_qt
- * [cap][2] = (queryIdx, trainIdx) in query order, distances [cap]; *count (device) = number kept. */
+ * [cap][2] = (queryIdx, trainIdx) in query order, distances [cap]; *count (device) = number kept.  The compare is
+ * double(dist0) < ratio * double(dist1): a query with one finite distance (dist1 = +inf) is kept, one with none is not. */
 int micv_bf_ratio_filter_dev(micv_ctx *ctx, const int32_t *idx2, const float *dist2, int nq,
                              double ratio, int32_t *matches_qt, float *distances, int64_t cap,
                              int64_t *count, micv_stream stream);

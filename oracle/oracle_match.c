@@ -10,7 +10,9 @@
 
 /* L2 distance, decision of this repository: d2 = fmaf chain of (a-b)^2 over the dimensions in
  * order, distance = sqrtf(d2).  Best two per query by (distance, train index) ascending -- what a
- * strict `<` scan of the train set in index order keeps. */
+ * strict `<` scan of the train set in index order keeps.  +inf is a distance like any other (an empty
+ * place is told by its index, not by the INFINITY it starts with); a NaN distance is never selected, and
+ * a place that stays empty reports index -1 and distance +inf. */
 void orc_bf_knn2(const float *query, int nq, size_t qstride, const float *train, int nt, size_t tstride,
                  int dim, int32_t *idx2, float *dist2) {
     for (int q = 0; q < nq; q++) {
@@ -24,8 +26,9 @@ void orc_bf_knn2(const float *query, int nq, size_t qstride, const float *train,
                 float diff = a[k] - b[k];
                 acc = fmaf(diff, diff, acc);
             }
-            if (acc < d0) { d1 = d0; i1 = i0; d0 = acc; i0 = t; }
-            else if (acc < d1) { d1 = acc; i1 = t; }
+            if (acc != acc) continue;
+            if (i0 < 0 || acc < d0) { d1 = d0; i1 = i0; d0 = acc; i0 = t; }
+            else if (i1 < 0 || acc < d1) { d1 = acc; i1 = t; }
         }
         idx2[2 * q] = i0; idx2[2 * q + 1] = i1;
         dist2[2 * q] = sqrtf(d0); dist2[2 * q + 1] = sqrtf(d1);

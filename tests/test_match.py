@@ -1,5 +1,8 @@
 """ps4 descriptor matching: brute-force 2-NN + ratio test.  Index outputs are
-bit-exact against the oracle; distances too (same fmaf chain, sqrtf correctly rounded)."""
+bit-exact against the oracle; distances too (same fmaf chain, sqrtf correctly rounded).
+The oracle comparison is one of two: oracle_match.c and Top2 in match.hip are the same text, so the matcher is also held,
+byte for byte, to tests/_ps4_feat_ref.py, which shares nothing with either (tests/test_ps4_feat_ref.py,
+tests/test_ps4_feat_paths_gpu.py)."""
 import ctypes as C
 
 import numpy as np

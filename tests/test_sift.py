@@ -1,6 +1,9 @@
 """The SIFT-style descriptor window (call site ps4_cpp/src/Solution.cpp:166-169; spec DESIGN.md §2).
 PARITY UNPINNED against OpenCV's SIFT (absent third-party code); what is tested: the oracle's own
-known-answer properties on the CPU, and bit-exact agreement of the HIP kernel with the oracle."""
+known-answer properties on the CPU, and bit-exact agreement of the HIP kernel with the oracle.
+The oracle comparison is one of two: oracle_sift.c and sift.hip are the same text, so the kernel is also held, byte for
+byte, to tests/_ps4_feat_ref.py, which shares nothing with either (tests/test_ps4_feat_ref.py,
+tests/test_ps4_feat_paths_gpu.py)."""
 import numpy as np
 import pytest
 
