@@ -509,6 +509,105 @@ int micv_generate_edge_host(micv_ctx *ctx, const uint8_t *src, int rows, int col
                             int gauss_size, double gauss_sigma, double low_thresh,
                             double high_thresh, uint8_t *edges, size_t estride);
 
+/* ------------------------------ ps1: circle search over a radius range ----------------- */
+
+/* The radius loops of the ps1 driver (ps1_cpp/src/main.cpp:173-180, :263-270, :299-307): for every radius r in
+ * [min_radius, max_radius], what micv_hough_circles_dev(r) followed by micv_hough_peaks_dev(num_peaks, threshold) gives --
+ * the votes of Hough.cu:85-93 and the peak rule of Hough.cu:148-157 with its exclusive upper bounds, peaks ordered by
+ * (votes descending, index ascending).  peaks_rc is u32 [n_radii][num_peaks][2] (row, col), counts i64 [n_radii] =
+ * min(num_peaks, candidates) (device memory in the _dev form); rows of peaks_rc past a radius' count are unspecified.
+ * acc, when not NULL, receives the accumulators, i32 [n_radii][rows][cols].  The edge-point list is built once, one grid
+ * covers (tile, radius), and with num_peaks <= 64 and acc == NULL no accumulator is written to memory: every tile
+ * applies the threshold and the peak rule on chip and hands on at most num_peaks keys.  The _dev form does not
+ * synchronise.  min_radius > max_radius is zero radii: MICV_OK, nothing written.  rows, cols <= 32767, num_peaks <= 4096. */
+int micv_hough_circles_range_peaks_dev(micv_ctx *ctx, const uint8_t *mask, int rows, int cols, size_t mstride,
+                                       unsigned min_radius, unsigned max_radius, unsigned num_peaks, int threshold,
+                                       uint32_t *peaks_rc, int64_t *counts, int32_t *acc, micv_stream stream);
+int micv_hough_circles_range_peaks_host(micv_ctx *ctx, const uint8_t *mask, int rows, int cols, size_t mstride,
+                                        unsigned min_radius, unsigned max_radius, unsigned num_peaks, int threshold,
+                                        uint32_t *peaks_rc, int64_t *counts, int32_t *acc);
+
+/* ------------------------------ ps1: pre-processing -------------------------------------- */
+
+/* sol::gaussianBlur, ps1_cpp/src/Solution.cpp:49-61, on CV_8UC1: cv::cuda::createGaussianFilter with
+ * getGaussianKernel(size, sigma, CV_32F) taps (odd size <= 31, sigma > 0), BORDER_REFLECT_101, row pass then column
+ * pass, each an fmaf chain from +0 with the taps ascending; round half to even and saturate at the end (the blur stage
+ * of micv_generate_edge_*). */
+int micv_gaussian_blur_u8_dev(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, int gauss_size,
+                              double gauss_sigma, uint8_t *dst, size_t dstride, micv_stream stream);
+int micv_gaussian_blur_u8_host(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, int gauss_size,
+                               double gauss_sigma, uint8_t *dst, size_t dstride);
+/* The same on CV_32FC1 (main.cpp:102, :144): float in, float out, no rounding. */
+int micv_gaussian_blur_f32_dev(micv_ctx *ctx, const float *src, int rows, int cols, size_t sstride, int gauss_size,
+                               double gauss_sigma, float *dst, size_t dstride, micv_stream stream);
+int micv_gaussian_blur_f32_host(micv_ctx *ctx, const float *src, int rows, int cols, size_t sstride, int gauss_size,
+                                double gauss_sigma, float *dst, size_t dstride);
+/* sol::generateEdge, Solution.cpp:21-47, as it runs on CV_32FC1 input (main.cpp:98, :107): the float blur, convertTo(CV_8U)
+ * = saturate_cast<uchar>(cvRound(v)) with cvRound half to even and NaN, +-inf and everything outside int -> INT_MIN -> 0
+ * (DESIGN.md section 2), then the Canny stages of micv_generate_edge_dev.  SYNCHRONISES `stream` as that call does. */
+int micv_generate_edge_f32_dev(micv_ctx *ctx, const float *src, int rows, int cols, size_t stride, int gauss_size,
+                               double gauss_sigma, double low_thresh, double high_thresh, uint8_t *edges, size_t estride,
+                               micv_stream stream);
+int micv_generate_edge_f32_host(micv_ctx *ctx, const float *src, int rows, int cols, size_t stride, int gauss_size,
+                                double gauss_sigma, double low_thresh, double high_thresh, uint8_t *edges,
+                                size_t estride);
+/* cv::erode with cv::getStructuringElement(MORPH_ELLIPSE, Size(ksize, ksize)), main.cpp:246-248, :282-284; ksize odd,
+ * 1..7.  Row i of the footprint (dy = i - r, r = ksize / 2) has half-width cvRound(r * sqrt((r*r - dy*dy) / r*r)), 0 when
+ * r = 0; anchor at the centre; BORDER_CONSTANT with morphologyDefaultBorderValue(): a tap outside the image is FLT_MAX
+ * (f32) or 255 (u8).  The minimum is v = first tap, then v = (x < v) ? x : v over the footprint in raster order: a NaN
+ * after the first tap never replaces, and of -0 / +0 the earlier one stays. */
+int micv_erode_ellipse_f32_dev(micv_ctx *ctx, const float *src, int rows, int cols, size_t sstride, int ksize, float *dst,
+                               size_t dstride, micv_stream stream);
+int micv_erode_ellipse_f32_host(micv_ctx *ctx, const float *src, int rows, int cols, size_t sstride, int ksize, float *dst,
+                                size_t dstride);
+int micv_erode_ellipse_u8_dev(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, int ksize,
+                              uint8_t *dst, size_t dstride, micv_stream stream);
+int micv_erode_ellipse_u8_host(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, int ksize,
+                               uint8_t *dst, size_t dstride);
+
+/* ------------------------------ ps1: after the peaks ------------------------------------- */
+
+/* sol::findParallelLines, Solution.cpp:134-173: of the first min(*count, max_peaks) (row, col) pairs of peaks_rc
+ * (max_peaks <= 4096), those whose key (row / delta_rho * delta_rho, col / delta_theta * delta_theta) -- unsigned
+ * integer division -- is shared by at least one other pair.  ORDER: the pairs come out in INPUT order; the reference
+ * emits them in the bucket order of libstdc++'s unordered_multimap, which is no property of the algorithm (every use
+ * draws the result in one colour, so no image depends on it).  delta_rho == 0 or delta_theta == 0 is MICV_EINVAL
+ * (the reference divides by zero).  out_rc holds up to max_peaks pairs; `count`, `out_count` are device words in the _dev form. */
+int micv_parallel_lines_dev(micv_ctx *ctx, const uint32_t *peaks_rc, const int64_t *count, unsigned max_peaks,
+                            unsigned delta_rho, unsigned delta_theta, uint32_t *out_rc, int64_t *out_count,
+                            micv_stream stream);
+int micv_parallel_lines_host(micv_ctx *ctx, const uint32_t *peaks_rc, int64_t count, unsigned delta_rho,
+                             unsigned delta_theta, uint32_t *out_rc, int64_t *out_count);
+/* cv::cvtColor(CV_GRAY2RGB) (main.cpp:88, :130, :167, :262, :298) of a MICV_DEPTH_8U or MICV_DEPTH_32F image to 8-bit,
+ * three interleaved channels; f32 goes through the saturate_cast<uchar> rule of micv_generate_edge_f32_*.  (The
+ * reference draws into a float image that cv::imwrite converts; converting first and drawing 8-bit colour gives the same file.) */
+int micv_gray_to_rgb8_dev(micv_ctx *ctx, const void *src, int depth, int rows, int cols, size_t sstride, uint8_t *dst,
+                          size_t dstride, micv_stream stream);
+int micv_gray_to_rgb8_host(micv_ctx *ctx, const void *src, int depth, int rows, int cols, size_t sstride, uint8_t *dst,
+                           size_t dstride);
+/* sol::rowColToRhoTheta + sol::drawLinesParametric, Solution.cpp:81-123, for the first min(*count, max_peaks) (row, col)
+ * peaks: rho = row * rho_bin - diag (diag of micv_hough_lines_dims), theta = col * theta_bin - 90, the end points of
+ * Solution.cpp:95-112 in float (sin / cos: the correctly rounded double function of the float radian, cast to float),
+ * Point2f -> Point by lrintf, then cv::line, thickness 1, LINE_8, as micv_viz::line walks it (one thread per major-axis
+ * step inside the image).  img is 8-bit, three interleaved channels, rows x cols; color = 3 bytes in memory order.
+ * Peaks with col * theta_bin >= 180 are not drawn. */
+int micv_draw_lines_parametric_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, size_t stride,
+                                   const uint32_t *peaks_rc, const int64_t *count, unsigned max_peaks, unsigned rho_bin,
+                                   unsigned theta_bin, const uint8_t *color, micv_stream stream);
+int micv_draw_lines_parametric_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, size_t stride,
+                                    const uint32_t *peaks_rc, int64_t count, unsigned rho_bin, unsigned theta_bin,
+                                    const uint8_t *color);
+/* sol::drawCircles, Solution.cpp:125-132, for the peaks of micv_hough_circles_range_peaks_*: peaks_rc u32
+ * [n_radii][num_peaks][2] (row, col), counts i64 [n_radii], circle j < min(counts[i], num_peaks) of radius index i has
+ * centre (col, row) and radius min_radius + i.  cv::circle, thickness 1, as its midpoint walk, every
+ * pixel bounds-checked.  Centres beyond 65535 in either coordinate are not drawn. */
+int micv_draw_circles_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, size_t stride, const uint32_t *peaks_rc,
+                          const int64_t *counts, unsigned n_radii, unsigned num_peaks, unsigned min_radius,
+                          const uint8_t *color, micv_stream stream);
+int micv_draw_circles_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, size_t stride, const uint32_t *peaks_rc,
+                           const int64_t *counts, unsigned n_radii, unsigned num_peaks, unsigned min_radius,
+                           const uint8_t *color);
+
 /* --------------------------- ps4: descriptor matching ----------- */
 
 /* cv::BFMatcher::create()->knnMatch(query, train, matches, 2), ps4_cpp/src/Solution.cpp:172-179:

@@ -156,6 +156,27 @@ SIGNATURES = {
     "micv_hough_peaks_host": (i32, [vp, vp, i32, i32, u32, i32, vp, vp]),
     # ps1 edge front-end
     "micv_generate_edge_dev": (i32, [vp, vp, i32, i32, sz, i32, f64, f64, f64, vp, sz, vp]),
+    # ps1 driver: radius-range circle search, pre-processing, overlays
+    "micv_hough_circles_range_peaks_dev": (i32, [vp, vp, i32, i32, sz, u32, u32, u32, i32, vp, vp, vp, vp]),
+    "micv_hough_circles_range_peaks_host": (i32, [vp, vp, i32, i32, sz, u32, u32, u32, i32, vp, vp, vp]),
+    "micv_gaussian_blur_u8_dev": (i32, [vp, vp, i32, i32, sz, i32, f64, vp, sz, vp]),
+    "micv_gaussian_blur_u8_host": (i32, [vp, vp, i32, i32, sz, i32, f64, vp, sz]),
+    "micv_gaussian_blur_f32_dev": (i32, [vp, vp, i32, i32, sz, i32, f64, vp, sz, vp]),
+    "micv_gaussian_blur_f32_host": (i32, [vp, vp, i32, i32, sz, i32, f64, vp, sz]),
+    "micv_generate_edge_f32_dev": (i32, [vp, vp, i32, i32, sz, i32, f64, f64, f64, vp, sz, vp]),
+    "micv_generate_edge_f32_host": (i32, [vp, vp, i32, i32, sz, i32, f64, f64, f64, vp, sz]),
+    "micv_erode_ellipse_f32_dev": (i32, [vp, vp, i32, i32, sz, i32, vp, sz, vp]),
+    "micv_erode_ellipse_f32_host": (i32, [vp, vp, i32, i32, sz, i32, vp, sz]),
+    "micv_erode_ellipse_u8_dev": (i32, [vp, vp, i32, i32, sz, i32, vp, sz, vp]),
+    "micv_erode_ellipse_u8_host": (i32, [vp, vp, i32, i32, sz, i32, vp, sz]),
+    "micv_parallel_lines_dev": (i32, [vp, vp, vp, u32, u32, u32, vp, vp, vp]),
+    "micv_parallel_lines_host": (i32, [vp, vp, i64, u32, u32, vp, C.POINTER(i64)]),
+    "micv_gray_to_rgb8_dev": (i32, [vp, vp, i32, i32, i32, sz, vp, sz, vp]),
+    "micv_gray_to_rgb8_host": (i32, [vp, vp, i32, i32, i32, sz, vp, sz]),
+    "micv_draw_lines_parametric_dev": (i32, [vp, vp, i32, i32, sz, vp, vp, u32, u32, u32, vp, vp]),
+    "micv_draw_lines_parametric_host": (i32, [vp, vp, i32, i32, sz, vp, i64, u32, u32, vp]),
+    "micv_draw_circles_dev": (i32, [vp, vp, i32, i32, sz, vp, vp, u32, u32, u32, vp, vp]),
+    "micv_draw_circles_host": (i32, [vp, vp, i32, i32, sz, vp, vp, u32, u32, u32, vp]),
     # ps4 matching
     "micv_bf_knn2_dev": (i32, [vp, vp, i32, sz, vp, i32, sz, i32, vp, vp, vp]),
     "micv_bf_ratio_filter_dev": (i32, [vp, vp, vp, i32, f64, vp, vp, i64, vp, vp]),

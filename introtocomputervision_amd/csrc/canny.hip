@@ -191,36 +191,19 @@ __global__ __launch_bounds__(256) void canny_edges_kernel(const unsigned long lo
 
 using namespace micv;
 
-extern "C" int micv_generate_edge_dev(micv_ctx *ctx, const uint8_t *src, int rows, int cols,
-                                      size_t stride, int gauss_size, double gauss_sigma,
-                                      double low_thresh, double high_thresh, uint8_t *edges,
-                                      size_t estride, micv_stream stream) {
-    MICV_REQUIRE(ctx && src && edges, "micv_generate_edge: null argument");
-    MICV_REQUIRE(rows > 0 && cols > 0 && stride >= (size_t)cols && estride >= (size_t)cols,
-                 "micv_generate_edge: bad size / stride");
-    MICV_REQUIRE(gauss_size >= 1 && gauss_size <= 31 && (gauss_size & 1) && gauss_sigma > 0,
-                 "micv_generate_edge: gaussian %d / sigma %g not supported (odd size <= 31, sigma > 0)",
-                 gauss_size, gauss_sigma);
-    MICV_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t n = (size_t)rows * cols;
+namespace micv {
+
+int launch_gauss_u8(hipStream_t s, const uint8_t *src, size_t stride, int rows, int cols, const Taps &t, uint8_t *dst,
+                    size_t dstride) {
+    gauss_u8_tiled_kernel<<<dim3(cdiv(cols, GB_TW), cdiv(rows, GB_TH)), 256, 0, s>>>(src, stride, rows, cols, t, dst, dstride);
+    MICV_LAUNCH_CHECK();
+    return MICV_OK;
+}
+
+// The Canny stages of sol::generateEdge on a blurred 8-bit plane; weak / strong: rows * cdiv(cols, 64) words each.
+int canny_from_u8(micv_ctx *ctx, hipStream_t s, const uint8_t *cin, size_t cstride, int rows, int cols, double low_thresh,
+                  double high_thresh, unsigned long long *weak, unsigned long long *strong, uint8_t *edges, size_t estride) {
     const int tiles_x = cdiv(cols, 64);
-    const size_t nwords = (size_t)rows * tiles_x;
-    void *scratch;
-    MICV_TRY(ctx->reserve(Carver::need(n, 1) + Carver::need(nwords, 8) * 2 + 256, &scratch));
-    Carver c(scratch);
-    uint8_t *blur = c.take<uint8_t>(n);
-    unsigned long long *weak = c.take<unsigned long long>(nwords), *strong = c.take<unsigned long long>(nwords);
-    const uint8_t *cin = src;
-    size_t cstride = stride;
-    if (gauss_size > 1) {  // a 1-tap Gaussian is the identity (Solution.cpp's problem-2 setting)
-        Taps t;
-        gaussian_taps(gauss_size, gauss_sigma, &t);
-        gauss_u8_tiled_kernel<<<dim3(cdiv(cols, GB_TW), cdiv(rows, GB_TH)), 256, 0, s>>>(src, stride, rows, cols, t, blur, (size_t)cols);
-        MICV_LAUNCH_CHECK();
-        cin = blur;
-        cstride = cols;
-    }
     double lo = low_thresh, hi = high_thresh;
     if (lo > hi) { const double tsw = lo; lo = hi; hi = tsw; }
     canny_gradmap_kernel<<<dim3(tiles_x, cdiv(rows, GM_TH)), 256, 0, s>>>(cin, cstride, rows, cols, (int)std::floor(lo), (int)std::floor(hi),
@@ -259,4 +242,38 @@ extern "C" int micv_generate_edge_dev(micv_ctx *ctx, const uint8_t *src, int row
     canny_edges_kernel<<<dim3(tiles_x, cdiv(rows, 4)), 256, 0, s>>>(strong, rows, cols, tiles_x, edges, estride);
     MICV_LAUNCH_CHECK();
     return MICV_OK;
+}
+
+}  // namespace micv
+
+extern "C" int micv_generate_edge_dev(micv_ctx *ctx, const uint8_t *src, int rows, int cols,
+                                      size_t stride, int gauss_size, double gauss_sigma,
+                                      double low_thresh, double high_thresh, uint8_t *edges,
+                                      size_t estride, micv_stream stream) {
+    MICV_REQUIRE(ctx && src && edges, "micv_generate_edge: null argument");
+    MICV_REQUIRE(rows > 0 && cols > 0 && stride >= (size_t)cols && estride >= (size_t)cols,
+                 "micv_generate_edge: bad size / stride");
+    MICV_REQUIRE(gauss_size >= 1 && gauss_size <= 31 && (gauss_size & 1) && gauss_sigma > 0,
+                 "micv_generate_edge: gaussian %d / sigma %g not supported (odd size <= 31, sigma > 0)",
+                 gauss_size, gauss_sigma);
+    MICV_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t n = (size_t)rows * cols;
+    const int tiles_x = cdiv(cols, 64);
+    const size_t nwords = (size_t)rows * tiles_x;
+    void *scratch;
+    MICV_TRY(ctx->reserve(Carver::need(n, 1) + Carver::need(nwords, 8) * 2 + 256, &scratch));
+    Carver c(scratch);
+    uint8_t *blur = c.take<uint8_t>(n);
+    unsigned long long *weak = c.take<unsigned long long>(nwords), *strong = c.take<unsigned long long>(nwords);
+    const uint8_t *cin = src;
+    size_t cstride = stride;
+    if (gauss_size > 1) {  // a 1-tap Gaussian is the identity (Solution.cpp's problem-2 setting)
+        Taps t;
+        gaussian_taps(gauss_size, gauss_sigma, &t);
+        MICV_TRY(launch_gauss_u8(s, src, stride, rows, cols, t, blur, (size_t)cols));
+        cin = blur;
+        cstride = cols;
+    }
+    return canny_from_u8(ctx, s, cin, cstride, rows, cols, low_thresh, high_thresh, weak, strong, edges, estride);
 }

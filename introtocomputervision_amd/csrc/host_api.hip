@@ -1325,4 +1325,146 @@ int micv_disparity_pair_display_host(micv_ctx *ctx, const float *left, const flo
                      image_left_inverted, image_right, istride);
 }
 
+// ---- ps1 driver (hough.hip's radius-range search, ps1.hip) ------------------------------------
+
+int micv_hough_circles_range_peaks_host(micv_ctx *ctx, const uint8_t *mask, int rows, int cols, size_t mstride,
+                                        unsigned min_radius, unsigned max_radius, unsigned num_peaks, int threshold,
+                                        uint32_t *peaks_rc, int64_t *counts, int32_t *acc) {
+    HOST_PROLOGUE("micv_hough_circles_range_peaks_host");
+    MICV_REQUIRE(mask && rows > 0 && cols > 0 && rows <= 32767 && cols <= 32767 && mstride >= (size_t)cols && num_peaks <= 4096,
+                 "micv_hough_circles_range_peaks_host: bad argument");
+    if (min_radius > max_radius) return MICV_OK;
+    MICV_REQUIRE(counts && (peaks_rc || num_peaks == 0), "micv_hough_circles_range_peaks_host: null output");
+    const size_t n_radii = (size_t)max_radius - min_radius + 1, cells = (size_t)rows * cols;
+    const size_t pbytes = n_radii * num_peaks * 8, abytes = acc ? n_radii * cells * 4 : 0;
+    DevBuf dm(cells), dp(pbytes + 8), dn(n_radii * 8), da(abytes + 8);
+    MICV_ALLOC_OK(dm); MICV_ALLOC_OK(dp); MICV_ALLOC_OK(dn); MICV_ALLOC_OK(da);
+    MICV_TRY(up2d(dm.p, mask, mstride, (size_t)cols, rows, s));
+    if (pbytes) MICV_HIP(hipMemsetAsync(dp.p, 0, pbytes, s));  // rows past a count are unspecified; the host copy gets zeros
+    MICV_TIMED("houghCirclesAccumulateKernel",
+               micv_hough_circles_range_peaks_dev(ctx, dm.as<uint8_t>(), rows, cols, cols, min_radius, max_radius, num_peaks,
+                                                  threshold, dp.as<uint32_t>(), dn.as<int64_t>(), acc ? da.as<int32_t>() : nullptr, s));
+    MICV_HIP(hipMemcpyAsync(counts, dn.p, n_radii * 8, hipMemcpyDeviceToHost, s));
+    if (pbytes) MICV_HIP(hipMemcpyAsync(peaks_rc, dp.p, pbytes, hipMemcpyDeviceToHost, s));
+    if (abytes) MICV_HIP(hipMemcpyAsync(acc, da.p, abytes, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+// one image in, one image out: upload, `call` on the device blocks (dense pitches), download
+#define PS1_IMAGE_HOST(fn, src, sstride, src_row_bytes, dst, dstride, dst_row_bytes, call)                  \
+    HOST_PROLOGUE(fn);                                                                                      \
+    MICV_REQUIRE(src && dst && rows > 0 && cols > 0 && sstride >= (size_t)(src_row_bytes) &&                \
+                     dstride >= (size_t)(dst_row_bytes),                                                    \
+                 fn ": bad argument");                                                                      \
+    DevBuf ds((size_t)rows * (src_row_bytes)), dd((size_t)rows * (dst_row_bytes));                          \
+    MICV_ALLOC_OK(ds); MICV_ALLOC_OK(dd);                                                                   \
+    MICV_TRY(up2d(ds.p, src, sstride, (size_t)(src_row_bytes), rows, s));                                   \
+    MICV_TRY(call);                                                                                         \
+    MICV_TRY(down2d(dst, dstride, dd.p, (size_t)(dst_row_bytes), rows, s));                                 \
+    MICV_HIP(hipStreamSynchronize(s));                                                                      \
+    return MICV_OK
+
+int micv_gaussian_blur_u8_host(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, int gauss_size,
+                               double gauss_sigma, uint8_t *dst, size_t dstride) {
+    PS1_IMAGE_HOST("micv_gaussian_blur_u8_host", src, sstride, cols, dst, dstride, cols,
+                   micv_gaussian_blur_u8_dev(ctx, ds.as<uint8_t>(), rows, cols, cols, gauss_size, gauss_sigma, dd.as<uint8_t>(), cols, s));
+}
+
+int micv_gaussian_blur_f32_host(micv_ctx *ctx, const float *src, int rows, int cols, size_t sstride, int gauss_size,
+                                double gauss_sigma, float *dst, size_t dstride) {
+    PS1_IMAGE_HOST("micv_gaussian_blur_f32_host", src, sstride, (size_t)cols * 4, dst, dstride, (size_t)cols * 4,
+                   micv_gaussian_blur_f32_dev(ctx, ds.as<float>(), rows, cols, (size_t)cols * 4, gauss_size, gauss_sigma, dd.as<float>(),
+                                              (size_t)cols * 4, s));
+}
+
+int micv_generate_edge_f32_host(micv_ctx *ctx, const float *src, int rows, int cols, size_t stride, int gauss_size,
+                                double gauss_sigma, double low_thresh, double high_thresh, uint8_t *edges,
+                                size_t estride) {
+    PS1_IMAGE_HOST("micv_generate_edge_f32_host", src, stride, (size_t)cols * 4, edges, estride, cols,
+                   micv_generate_edge_f32_dev(ctx, ds.as<float>(), rows, cols, (size_t)cols * 4, gauss_size, gauss_sigma, low_thresh,
+                                              high_thresh, dd.as<uint8_t>(), cols, s));
+}
+
+int micv_erode_ellipse_f32_host(micv_ctx *ctx, const float *src, int rows, int cols, size_t sstride, int ksize, float *dst,
+                                size_t dstride) {
+    PS1_IMAGE_HOST("micv_erode_ellipse_f32_host", src, sstride, (size_t)cols * 4, dst, dstride, (size_t)cols * 4,
+                   micv_erode_ellipse_f32_dev(ctx, ds.as<float>(), rows, cols, (size_t)cols * 4, ksize, dd.as<float>(), (size_t)cols * 4, s));
+}
+
+int micv_erode_ellipse_u8_host(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, int ksize,
+                               uint8_t *dst, size_t dstride) {
+    PS1_IMAGE_HOST("micv_erode_ellipse_u8_host", src, sstride, cols, dst, dstride, cols,
+                   micv_erode_ellipse_u8_dev(ctx, ds.as<uint8_t>(), rows, cols, cols, ksize, dd.as<uint8_t>(), cols, s));
+}
+
+int micv_gray_to_rgb8_host(micv_ctx *ctx, const void *src, int depth, int rows, int cols, size_t sstride, uint8_t *dst,
+                           size_t dstride) {
+    MICV_REQUIRE(depth == MICV_DEPTH_8U || depth == MICV_DEPTH_32F, "micv_gray_to_rgb8_host: depth %d not supported (8U, 32F)", depth);
+    const size_t es = depth == MICV_DEPTH_8U ? 1 : 4;
+    PS1_IMAGE_HOST("micv_gray_to_rgb8_host", src, sstride, (size_t)cols * es, dst, dstride, (size_t)cols * 3,
+                   micv_gray_to_rgb8_dev(ctx, ds.p, depth, rows, cols, (size_t)cols * es, dd.as<uint8_t>(), (size_t)cols * 3, s));
+}
+
+int micv_parallel_lines_host(micv_ctx *ctx, const uint32_t *peaks_rc, int64_t count, unsigned delta_rho,
+                             unsigned delta_theta, uint32_t *out_rc, int64_t *out_count) {
+    HOST_PROLOGUE("micv_parallel_lines_host");
+    MICV_REQUIRE(out_count && count >= 0 && count <= 4096 && ((peaks_rc && out_rc) || count == 0),
+                 "micv_parallel_lines_host: bad argument (<= 4096 peaks)");
+    MICV_REQUIRE(delta_rho > 0 && delta_theta > 0, "micv_parallel_lines_host: delta_rho and delta_theta must be positive");
+    DevBuf dp((size_t)count * 8 + 8), dout((size_t)count * 8 + 8), dn(16);
+    MICV_ALLOC_OK(dp); MICV_ALLOC_OK(dout); MICV_ALLOC_OK(dn);
+    if (count) MICV_HIP(hipMemcpyAsync(dp.p, peaks_rc, (size_t)count * 8, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(dn.p, &count, 8, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_parallel_lines_dev(ctx, dp.as<uint32_t>(), dn.as<int64_t>(), (unsigned)count, delta_rho, delta_theta,
+                                     dout.as<uint32_t>(), dn.as<int64_t>() + 1, s));
+    MICV_HIP(hipMemcpyAsync(out_count, dn.as<int64_t>() + 1, 8, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    if (*out_count > 0) MICV_HIP(hipMemcpy(out_rc, dout.p, (size_t)*out_count * 8, hipMemcpyDeviceToHost));
+    return MICV_OK;
+}
+
+int micv_draw_lines_parametric_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, size_t stride,
+                                    const uint32_t *peaks_rc, int64_t count, unsigned rho_bin, unsigned theta_bin,
+                                    const uint8_t *color) {
+    HOST_PROLOGUE("micv_draw_lines_parametric_host");
+    MICV_REQUIRE(img && color && rows > 0 && cols > 0 && stride >= (size_t)cols * 3 && count >= 0 && count <= 4096 &&
+                     (peaks_rc || count == 0),
+                 "micv_draw_lines_parametric_host: bad argument (<= 4096 peaks)");
+    const size_t rb = (size_t)cols * 3;
+    DevBuf di((size_t)rows * rb), dp((size_t)count * 8 + 8), dn(8);
+    MICV_ALLOC_OK(di); MICV_ALLOC_OK(dp); MICV_ALLOC_OK(dn);
+    MICV_TRY(up2d(di.p, img, stride, rb, rows, s));
+    if (count) MICV_HIP(hipMemcpyAsync(dp.p, peaks_rc, (size_t)count * 8, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(dn.p, &count, 8, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_draw_lines_parametric_dev(ctx, di.as<uint8_t>(), rows, cols, rb, dp.as<uint32_t>(), dn.as<int64_t>(), (unsigned)count,
+                                            rho_bin, theta_bin, color, s));
+    MICV_TRY(down2d(img, stride, di.p, rb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_draw_circles_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, size_t stride, const uint32_t *peaks_rc,
+                           const int64_t *counts, unsigned n_radii, unsigned num_peaks, unsigned min_radius,
+                           const uint8_t *color) {
+    HOST_PROLOGUE("micv_draw_circles_host");
+    MICV_REQUIRE(img && color && rows > 0 && cols > 0 && stride >= (size_t)cols * 3 && num_peaks <= 4096 &&
+                     (unsigned long long)n_radii * num_peaks < (1ull << 31),
+                 "micv_draw_circles_host: bad argument");
+    const size_t total = (size_t)n_radii * num_peaks;
+    if (total == 0) return MICV_OK;
+    MICV_REQUIRE(peaks_rc && counts, "micv_draw_circles_host: null argument");
+    const size_t rb = (size_t)cols * 3;
+    DevBuf di((size_t)rows * rb), dp(total * 8), dn((size_t)n_radii * 8);
+    MICV_ALLOC_OK(di); MICV_ALLOC_OK(dp); MICV_ALLOC_OK(dn);
+    MICV_TRY(up2d(di.p, img, stride, rb, rows, s));
+    MICV_HIP(hipMemcpyAsync(dp.p, peaks_rc, total * 8, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(dn.p, counts, (size_t)n_radii * 8, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_draw_circles_dev(ctx, di.as<uint8_t>(), rows, cols, rb, dp.as<uint32_t>(), dn.as<int64_t>(), n_radii, num_peaks,
+                                   min_radius, color, s));
+    MICV_TRY(down2d(img, stride, di.p, rb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
 }  // extern "C"

@@ -421,7 +421,234 @@ __global__ void peak_emit_kernel(const unsigned long long *__restrict__ sel, uns
     *count = n;
 }
 
-static size_t hough_diag(int rows, int cols) {
+// ---- the circle search over a radius range (ps1_cpp/src/main.cpp:173-180, :263-270, :299-307) in one grid --------
+// blockIdx.z is the radius.  The votes are those of hough_circles_tiled_kernel; the tile is staged with a one-cell apron
+// up and left (the cells the 2x2 rule of PeakPred reads beyond the tile: they belong to the neighbouring tiles and are
+// voted again here), so the threshold and the local-maximum rule run on LDS and the accumulator need not exist in HBM.
+// The keys (votes, index) are distinct, so the K largest of a radius are among the K largest of every tile: a tile
+// appends its own top K (at most) to the radius' key list -- tiles x K slots, whatever the input -- and
+// peak_select_keys_kernel picks the K largest of the list.
+constexpr int RK_MAX = 64;  // the fused form serves num_peaks <= 64, as peak_select_all_kernel does
+template <bool WRITE_ACC, bool PEAKS>
+__global__ __launch_bounds__(1024) void hough_circles_range_kernel(
+    const int32_t *__restrict__ pts, const int64_t *__restrict__ npts_p, int rows, int cols, const float *__restrict__ ct,
+    const float *__restrict__ st, unsigned radius0, int32_t *__restrict__ acc, int threshold, unsigned num_peaks,
+    unsigned long long *__restrict__ keys, size_t key_cap, unsigned *__restrict__ nkeys) {
+    constexpr int TA = 64, TB = 32, HW = TA + 1, HH = TB + 1, CH = 2048, NT = 1024;
+    __shared__ int hist[HW * HH];
+    __shared__ __attribute__((aligned(8))) int list[4 * CH];  // (point, quadrant) entries; the per-wave top keys afterwards
+    __shared__ int nlist;
+    __shared__ unsigned ntile;
+    __shared__ long long range[2];
+    __shared__ float tc[360], ts[360];
+    const int tid = threadIdx.x;
+    const int a0 = blockIdx.x * TA, b0 = blockIdx.y * TB;
+    const int ea0 = a0 - 1, eb0 = b0 - 1;  // the staged window [ea0, ea0 + HW) x [eb0, eb0 + HH)
+    const unsigned radius_u = radius0 + blockIdx.z;
+    const float radius = (float)radius_u;
+    // reach of micv_hough_circles_band_dev; the window is one cell larger than the tile on its low sides only, and the
+    // filters below are written against the window, so they grow by that cell
+    const long long reach_l = (long long)radius_u + 1 < (long long)rows + cols ? (long long)radius_u + 1 : (long long)rows + cols;
+    const int reach = (int)reach_l;
+    for (int i = tid; i < HW * HH; i += NT) hist[i] = 0;
+    if (tid == 0) ntile = 0;
+    if (tid < 128) {  // the 64-ary search of hough_circles_tiled_kernel over the window's rows
+        const int wv = tid >> 6, ln = tid & 63;
+        const long long yl = wv == 0 ? (long long)eb0 - reach : (long long)eb0 + HH + reach;
+        const long long key = yl <= 0 ? 0 : yl * cols;
+        long long lo = 0, hi = *npts_p;
+        while (hi - lo > 64) {
+            const long long stride = (hi - lo + 63) >> 6;
+            const long long at = lo + (ln + 1) * stride - 1;
+            const bool below = at < hi && (long long)pts[at] < key;
+            const int c = __popcll(__ballot(below));
+            lo += c * stride;
+            hi = lo + stride < hi ? lo + stride : hi;
+        }
+        const bool below = lo + ln < hi && (long long)pts[lo + ln] < key;
+        lo += __popcll(__ballot(below));
+        if (ln == 0) range[wv] = lo;
+    }
+    for (int i = tid; i < 360; i += NT) {
+        tc[i] = ct[i];
+        ts[i] = st[i];
+    }
+    // cells of the window a vote may land in (Hough.cu:89: 0 < a < cols, 0 < b < rows -- apron cells included)
+    const unsigned amin = ea0 > 1 ? ea0 : 1, bmin = eb0 > 1 ? eb0 : 1;
+    const unsigned amax = a0 + TA < cols ? a0 + TA : cols, bmax = b0 + TB < rows ? b0 + TB : rows;
+    const unsigned aw = amax > amin ? amax - amin : 0, bw = bmax > bmin ? bmax - bmin : 0;
+    __syncthreads();
+    const long long lo = range[0], hi = range[1];
+    for (long long base = lo; base < hi; base += CH) {
+        if (tid == 0) nlist = 0;
+        __syncthreads();
+        const long long end = base + CH < hi ? base + CH : hi;
+        for (long long i = base + tid; i < end; i += NT) {
+            const int p = pts[i];
+            const int y = p / cols, x = p - y * cols;
+            if (x >= ea0 - reach && x < ea0 + HW + reach) {
+                const bool lft = x >= ea0, rgt = x <= ea0 + HW, up = y >= eb0, dwn = y <= eb0 + HH;  // (quadrants: see the tiled kernel)
+                const int e = (y << 15) | x;
+                if (lft && up) list[atomicAdd(&nlist, 1)] = e;
+                if (rgt && up) list[atomicAdd(&nlist, 1)] = e | (1 << 30);
+                if (rgt && dwn) list[atomicAdd(&nlist, 1)] = e | (2 << 30);
+                if (lft && dwn) list[atomicAdd(&nlist, 1)] = e | (3 << 30);
+            }
+        }
+        __syncthreads();
+        const int nv = nlist * 90;
+        for (int w = tid; w < nv; w += NT) {
+            const int k = w / 90;
+            const unsigned e = (unsigned)list[k];
+            const int t = (w - k * 90) + 90 * (int)(e >> 30);
+            const float fx = (float)(e & 0x7FFF), fy = (float)((e >> 15) & 0x7FFF);
+            unsigned a, b;  // v_cvt_u32_f32 saturates: it is f2u_sat
+            const float va = fx - radius * tc[t], vb = fy - radius * ts[t];
+            asm("v_cvt_u32_f32 %0, %1" : "=v"(a) : "v"(va));
+            asm("v_cvt_u32_f32 %0, %1" : "=v"(b) : "v"(vb));
+            const unsigned la = a - amin, lb = b - bmin;
+            if (la < aw && lb < bw) atomicAdd(&hist[((int)b - eb0) * HW + ((int)a - ea0)], 1);
+        }
+        __syncthreads();
+    }
+    if (WRITE_ACC) {
+        int32_t *out = acc + (size_t)blockIdx.z * rows * cols;
+        for (int i = tid; i < TA * TB; i += NT) {
+            const int la = i & (TA - 1), lb = i / TA, a = a0 + la, b = b0 + lb;
+            if (a < cols && b < rows) out[(size_t)b * cols + a] = hist[(lb + 1) * HW + la + 1];
+        }
+    }
+    if (!PEAKS) return;
+    // PeakPred on the staged window: two cells per thread, key 0 = no candidate (a real key is never 0)
+    unsigned long long key[2];
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int i = tid + j * NT, la = i & (TA - 1), lb = i / TA, tx = a0 + la, ty = b0 + lb;
+        key[j] = 0;
+        if (tx < cols && ty < rows) {
+            const int v = hist[(lb + 1) * HW + la + 1];
+            if (v >= threshold) {
+                const int y1 = rows - 1 < ty + 1 ? rows - 1 : ty + 1;  // exclusive bounds, as written
+                const int x1 = cols - 1 < tx + 1 ? cols - 1 : tx + 1;
+                bool is_max = true;
+                for (int y = ty - 1 > 0 ? ty - 1 : 0; y < y1; y++)
+                    for (int x = tx - 1 > 0 ? tx - 1 : 0; x < x1; x++)
+                        if (hist[(y - eb0) * HW + (x - ea0)] > v) is_max = false;
+                if (is_max) key[j] = peak_key(v, (uint32_t)ty * (uint32_t)cols + (uint32_t)tx);
+            }
+        }
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+    const int mine = __popcll(__ballot(key[0] != 0)) + __popcll(__ballot(key[1] != 0));
+    if (lane == 0 && mine) atomicAdd(&ntile, (unsigned)mine);
+    __syncthreads();  // (also: every read of `list` is behind this barrier)
+    const unsigned nc = ntile;
+    if (nc == 0) return;  // (uniform)
+    unsigned long long *top = reinterpret_cast<unsigned long long *>(list);  // [16][RK_MAX]
+    unsigned long long bound = ~0ull;
+    for (unsigned k = 0; k < num_peaks; k++) {  // the wave's own top K, descending; 0 once it runs out
+        unsigned long long m = 0;
+#pragma unroll
+        for (int j = 0; j < 2; j++) m = key[j] < bound && key[j] > m ? key[j] : m;
+        m = wave_max_u64(m);
+        if (lane == 0) top[wave * RK_MAX + k] = m;
+        bound = m ? m : 1ull;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    const unsigned emit = nc < num_peaks ? nc : num_peaks;  // sum over waves of min(K, c_wave) >= min(K, c_tile)
+    unsigned slot = 0;
+    if (lane == 0) slot = atomicAdd(&nkeys[blockIdx.z], emit);
+    slot = (unsigned)__builtin_amdgcn_readfirstlane((int)slot);
+    unsigned long long *out = keys + (size_t)blockIdx.z * key_cap + slot;
+    bound = ~0ull;
+    for (unsigned k = 0; k < emit; k++) {
+        unsigned long long m = 0;
+        for (unsigned t = lane; t < 16 * num_peaks; t += 64) {
+            const unsigned long long c = top[(t / num_peaks) * RK_MAX + t % num_peaks];
+            m = c < bound && c > m ? c : m;
+        }
+        m = wave_max_u64(m);
+        if (lane == 0) out[k] = m;
+        bound = m;
+    }
+}
+
+// One workgroup per radius: the num_peaks (<= 64) largest of the radius' key list, as peak_select_all_kernel selects
+// them (up to 4096 keys: every wave's top K from registers, then wave 0 over the 16 x K survivors; longer lists are
+// scanned again every round).  count = the rounds that found a key = min(num_peaks, candidates).
+__global__ __launch_bounds__(1024) void peak_select_keys_kernel(const unsigned long long *__restrict__ keys, size_t key_cap,
+                                                                const unsigned *__restrict__ nkeys, unsigned num_peaks, int cols,
+                                                                uint32_t *__restrict__ peaks_rc, int64_t *__restrict__ count) {
+    constexpr int KEEP = 4096;
+    __shared__ unsigned long long top[16 * RK_MAX];
+    __shared__ unsigned long long wmax[16];
+    const unsigned long long *kz = keys + (size_t)blockIdx.x * key_cap;
+    uint32_t *out = peaks_rc + (size_t)blockIdx.x * num_peaks * 2;
+    const int64_t n = nkeys[blockIdx.x];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    auto emit = [&](int64_t at, unsigned long long m) {
+        const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(m & 0xFFFFFFFFull);
+        out[2 * at] = idx / (uint32_t)cols;
+        out[2 * at + 1] = idx % (uint32_t)cols;
+    };
+    int64_t found = 0;
+    unsigned long long bound = ~0ull;
+    if (n <= KEEP) {
+        unsigned long long key[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int64_t i = wave * 256 + j * 64 + lane;
+            key[j] = i < n ? kz[i] : 0ull;
+        }
+        for (unsigned k = 0; k < num_peaks; k++) {
+            unsigned long long m = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) m = key[j] < bound && key[j] > m ? key[j] : m;
+            m = wave_max_u64(m);
+            if (lane == 0) top[wave * RK_MAX + k] = m;
+            bound = m ? m : 1ull;
+        }
+        __syncthreads();
+        if (wave != 0) return;
+        bound = ~0ull;
+        for (unsigned k = 0; k < num_peaks; k++) {
+            unsigned long long m = 0;
+            for (unsigned t = lane; t < 16 * num_peaks; t += 64) {
+                const unsigned long long c = top[(t / num_peaks) * RK_MAX + t % num_peaks];
+                m = c < bound && c > m ? c : m;
+            }
+            m = wave_max_u64(m);
+            if (m == 0) break;
+            if (lane == 0) emit(found, m);
+            bound = m;
+            found++;
+        }
+        if (lane == 0) count[blockIdx.x] = found;
+        return;
+    }
+    for (unsigned k = 0; k < num_peaks; k++) {
+        unsigned long long m = 0;
+        for (int64_t i = threadIdx.x; i < n; i += 1024) {
+            const unsigned long long c = kz[i];
+            if (c < bound && c > m) m = c;
+        }
+        m = wave_max_u64(m);
+        if (lane == 0) wmax[wave] = m;
+        __syncthreads();
+        m = wmax[0];
+#pragma unroll
+        for (int w = 1; w < 16; w++) m = wmax[w] > m ? wmax[w] : m;
+        __syncthreads();
+        if (m == 0) break;
+        if (threadIdx.x == 0) emit(found, m);
+        bound = m;
+        found++;
+    }
+    if (threadIdx.x == 0) count[blockIdx.x] = found;
+}
+
+size_t hough_diag(int rows, int cols) {
     return (size_t)std::ceil(std::sqrt((double)(rows * rows + cols * cols)));  // Hough.cu:258-259
 }
 
@@ -561,22 +788,14 @@ int micv_hough_circles_band_dev(micv_ctx *ctx, const uint8_t *mask, int band_row
     return MICV_OK;
 }
 
-int micv_hough_peaks_dev(micv_ctx *ctx, const int32_t *acc, int rows, int cols,
-                         unsigned num_peaks, int threshold, uint32_t *peaks_rc, int64_t *count,
-                         micv_stream stream) {
-    MICV_REQUIRE(ctx && acc && count, "micv_hough_peaks: null argument");
-    MICV_REQUIRE(peaks_rc || num_peaks == 0, "micv_hough_peaks: peaks_rc is null");
-    MICV_REQUIRE(rows > 0 && cols > 0 && (int64_t)rows * cols < ((int64_t)1 << 31),
-                 "micv_hough_peaks: bad size %dx%d", rows, cols);
-    MICV_REQUIRE(num_peaks <= 4096, "micv_hough_peaks: num_peaks %u > 4096 not supported",
-                 num_peaks);
-    MICV_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+static size_t hough_peaks_scratch_bytes(int64_t n, unsigned num_peaks) {
+    return Carver::need(n, 4) + Carver::need(1, 8) + Carver::need((size_t)num_peaks + 1, 8) + compact_scratch_bytes(n);
+}
+
+// findLocalMaxima on `scratch` (hough_peaks_scratch_bytes): micv_hough_peaks_dev behind its argument checks
+static int hough_peaks_at(micv_ctx *ctx, hipStream_t s, const int32_t *acc, int rows, int cols, unsigned num_peaks,
+                          int threshold, uint32_t *peaks_rc, int64_t *count, void *scratch) {
     const int64_t n = (int64_t)rows * cols;
-    void *scratch;
-    MICV_TRY(ctx->reserve(Carver::need(n, 4) + Carver::need(1, 8) +
-                              Carver::need((size_t)num_peaks + 1, 8) + compact_scratch_bytes(n),
-                          &scratch));
     Carver c(scratch);
     int32_t *cand = c.take<int32_t>(n);
     int64_t *ncand = c.take<int64_t>(1);
@@ -594,6 +813,92 @@ int micv_hough_peaks_dev(micv_ctx *ctx, const int32_t *acc, int rows, int cols,
     }
     peak_emit_kernel<<<1, 64, 0, s>>>(sel, num_peaks, cols, peaks_rc, count);
     MICV_LAUNCH_CHECK();
+    return MICV_OK;
+}
+
+int micv_hough_peaks_dev(micv_ctx *ctx, const int32_t *acc, int rows, int cols,
+                         unsigned num_peaks, int threshold, uint32_t *peaks_rc, int64_t *count,
+                         micv_stream stream) {
+    MICV_REQUIRE(ctx && acc && count, "micv_hough_peaks: null argument");
+    MICV_REQUIRE(peaks_rc || num_peaks == 0, "micv_hough_peaks: peaks_rc is null");
+    MICV_REQUIRE(rows > 0 && cols > 0 && (int64_t)rows * cols < ((int64_t)1 << 31),
+                 "micv_hough_peaks: bad size %dx%d", rows, cols);
+    MICV_REQUIRE(num_peaks <= 4096, "micv_hough_peaks: num_peaks %u > 4096 not supported",
+                 num_peaks);
+    MICV_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    void *scratch;
+    MICV_TRY(ctx->reserve(hough_peaks_scratch_bytes((int64_t)rows * cols, num_peaks), &scratch));
+    return hough_peaks_at(ctx, s, acc, rows, cols, num_peaks, threshold, peaks_rc, count, scratch);
+}
+
+int micv_hough_circles_range_peaks_dev(micv_ctx *ctx, const uint8_t *mask, int rows, int cols, size_t mstride,
+                                       unsigned min_radius, unsigned max_radius, unsigned num_peaks, int threshold,
+                                       uint32_t *peaks_rc, int64_t *counts, int32_t *acc, micv_stream stream) {
+    MICV_REQUIRE(ctx && mask, "micv_hough_circles_range_peaks: null argument");
+    MICV_REQUIRE(rows > 0 && cols > 0 && rows <= 32767 && cols <= 32767,
+                 "micv_hough_circles_range_peaks: bad size %dx%d", rows, cols);
+    MICV_REQUIRE(mstride >= (size_t)cols, "micv_hough_circles_range_peaks: bad stride");
+    MICV_REQUIRE(num_peaks <= 4096, "micv_hough_circles_range_peaks: num_peaks %u > 4096 not supported", num_peaks);
+    if (min_radius > max_radius) return MICV_OK;  // zero radii: nothing is written
+    MICV_REQUIRE(counts && (peaks_rc || num_peaks == 0), "micv_hough_circles_range_peaks: null output");
+    MICV_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const unsigned long long n_radii = (unsigned long long)max_radius - min_radius + 1;
+    const size_t cells = (size_t)rows * cols;
+    const dim3 tiles(cdiv(cols, 64), cdiv(rows, 32));
+    const size_t ntiles = (size_t)tiles.x * tiles.y;
+    const bool fused = num_peaks >= 1 && num_peaks <= RK_MAX;
+    const bool per_radius = num_peaks > RK_MAX;  // accumulators, then the existing peak path radius by radius
+    // scratch per radius of a chunk: the key list and its length (fused), or an accumulator plane when the caller
+    // keeps none (per_radius); a chunk is as many radii as fit ~256 MiB and the grid's z dimension
+    const size_t key_cap = fused ? ntiles * num_peaks : 0;
+    const size_t per_z = fused ? key_cap * 8 + 4 : (per_radius && !acc ? cells * 4 : 0);
+    unsigned long long chunk = std::min<unsigned long long>(n_radii, 65535);
+    if (per_z) chunk = std::max<unsigned long long>(1, std::min<unsigned long long>(chunk, (size_t(256) << 20) / per_z));
+    const size_t peaks_bytes = per_radius ? hough_peaks_scratch_bytes((int64_t)cells, num_peaks) : 0;
+    const size_t extra_bytes = Carver::need(chunk * key_cap, 8) + Carver::need(chunk, 4) +
+                               Carver::need(per_radius && !acc ? chunk * cells : 0, 4) + peaks_bytes;
+    int32_t *pts;
+    int64_t *npts;
+    char *extra;
+    MICV_TRY(hough_points(ctx, s, mask, rows, cols, mstride, extra_bytes, &pts, &npts, &extra));  // the one point list
+    Carver c(extra);
+    unsigned long long *keys = c.take<unsigned long long>(chunk * key_cap);
+    unsigned *nkeys = c.take<unsigned>(chunk);
+    int32_t *tmp_acc = c.take<int32_t>(per_radius && !acc ? chunk * cells : 0);
+    void *peaks_scratch = c.base + c.off;
+    const TrigTable *dt;
+    MICV_TRY(trig_on_device(ctx, 1, 0, &dt));
+    if (num_peaks == 0) MICV_HIP(hipMemsetAsync(counts, 0, n_radii * 8, s));
+    for (unsigned long long z0 = 0; z0 < n_radii; z0 += chunk) {
+        const unsigned nz = (unsigned)std::min<unsigned long long>(chunk, n_radii - z0);
+        const unsigned r0 = min_radius + (unsigned)z0;
+        const dim3 grid(tiles.x, tiles.y, nz);
+        int32_t *az = acc ? acc + (size_t)z0 * cells : tmp_acc;
+        uint32_t *pz = peaks_rc ? peaks_rc + (size_t)z0 * num_peaks * 2 : nullptr;
+        if (fused) {
+            MICV_HIP(hipMemsetAsync(nkeys, 0, (size_t)nz * 4, s));
+            if (acc)
+                hough_circles_range_kernel<true, true><<<grid, 1024, 0, s>>>(pts, npts, rows, cols, dt->c, dt->s, r0, az, threshold,
+                                                                             num_peaks, keys, key_cap, nkeys);
+            else
+                hough_circles_range_kernel<false, true><<<grid, 1024, 0, s>>>(pts, npts, rows, cols, dt->c, dt->s, r0, nullptr,
+                                                                              threshold, num_peaks, keys, key_cap, nkeys);
+            MICV_LAUNCH_CHECK();
+            peak_select_keys_kernel<<<nz, 1024, 0, s>>>(keys, key_cap, nkeys, num_peaks, cols, pz, counts + z0);
+            MICV_LAUNCH_CHECK();
+            continue;
+        }
+        if (!acc && !per_radius) continue;  // num_peaks == 0 and no accumulator asked for
+        hough_circles_range_kernel<true, false><<<grid, 1024, 0, s>>>(pts, npts, rows, cols, dt->c, dt->s, r0, az, threshold, 0,
+                                                                      nullptr, 0, nullptr);
+        MICV_LAUNCH_CHECK();
+        if (per_radius)
+            for (unsigned z = 0; z < nz; z++)
+                MICV_TRY(hough_peaks_at(ctx, s, az + (size_t)z * cells, rows, cols, num_peaks, threshold,
+                                        pz + (size_t)z * num_peaks * 2, counts + z0 + z, peaks_scratch));
+    }
     return MICV_OK;
 }
 

@@ -44,4 +44,13 @@ int launch_warp(hipStream_t s, const float *src, int sstride, const float *du, c
 int launch_pyr_up_batch(hipStream_t s, const float *src_u, const float *src_v, int rows, int cols, size_t src_img,
                         float *dst_u, float *dst_v, size_t dst_img, float scale, int batch);
 
+// canny.hip: the u8 Gaussian blur of sol::generateEdge / sol::gaussianBlur, and the Canny stages behind it on a blurred
+// 8-bit plane (weak / strong: rows * cdiv(cols, 64) words of scratch each; synchronises `s` like micv_generate_edge_dev).
+int launch_gauss_u8(hipStream_t s, const uint8_t *src, size_t stride, int rows, int cols, const Taps &t, uint8_t *dst,
+                    size_t dstride);
+int canny_from_u8(micv_ctx *ctx, hipStream_t s, const uint8_t *cin, size_t cstride, int rows, int cols, double low_thresh,
+                  double high_thresh, unsigned long long *weak, unsigned long long *strong, uint8_t *edges, size_t estride);
+// hough.hip: maxDist of Hough.cu:258-259
+size_t hough_diag(int rows, int cols);
+
 }  // namespace micv

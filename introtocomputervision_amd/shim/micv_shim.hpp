@@ -50,7 +50,7 @@ using Scalar = cv::Scalar;
 // cv::cuda::GpuMat's data pointer must be memory this library's device can address (an OpenCV
 // built against HIP, or unified memory); the overloads below only pass it through.
 using GpuMat = cv::cuda::GpuMat;
-enum { F32 = CV_32F, S8 = CV_8S, U8 = CV_8U, S32 = CV_32S };
+enum { F32 = CV_32F, S8 = CV_8S, U8 = CV_8U, S32 = CV_32S, U8C3 = CV_8UC3 };
 inline micv_ctx *context() {  // one context per thread, like the reference's per-call streams
     thread_local micv_ctx *ctx = nullptr;
     if (!ctx && micv_ctx_create(0, &ctx) != MICV_OK)
@@ -68,7 +68,7 @@ using Point2f = micv::Point2f;
 using Size = micv::Size;
 using Scalar = micv::Scalar;
 using GpuMat = micv::GpuMat;
-enum { F32 = micv::CV_32F, S8 = micv::CV_8S, U8 = micv::CV_8U, S32 = micv::CV_32S };
+enum { F32 = micv::CV_32F, S8 = micv::CV_8S, U8 = micv::CV_8U, S32 = micv::CV_32S, U8C3 = micv::CV_8UC3 };
 inline micv_ctx *context() { return micv::thread_context(); }
 inline void create_continuous(GpuMat &m, int rows, int cols, int type) { m.create(rows, cols, type); }
 }  // namespace micv_shim
@@ -864,15 +864,198 @@ inline void plotConfusionMatrix(const Mat &confusion, const std::string &title, 
 
 namespace sol {
 using micv_shim::Mat;
-// sol::generateEdge, ps1_cpp/src/Solution.cpp:21-47, with Config::EdgeDetect spelled out
-// (gaussianSize, gaussianSigma, lowerThreshold, upperThreshold; Sobel aperture 3).
+// The functions of ps1_cpp/src/Solution.h:19-75 with Config::EdgeDetect / Config::HoughLines / Config::Hough spelled
+// out (gaussianSize, gaussianSigma, lowerThreshold, upperThreshold; rhoBinSize, thetaBinSize; numPeaks, threshold).
+//
+// sol::generateEdge, Solution.h:19, Solution.cpp:21-47 (Sobel aperture 3): CV_8UC1, or CV_32FC1 as problems 4-8 pass it
+// (main.cpp:98, :107) -- ONE function that looks at the type at run time.
 inline void generateEdge(const Mat &input, const int gaussianSize, const double gaussianSigma,
                          const double lowerThreshold, const double upperThreshold, Mat &output) {
-    micv_shim::require(input.type() == micv_shim::U8, "sol::generateEdge: CV_8UC1 expected");
+    micv_shim::require(input.type() == micv_shim::U8 || input.type() == micv_shim::F32,
+                       "sol::generateEdge: CV_8UC1 or CV_32FC1 expected");
     Mat out(input.rows, input.cols, micv_shim::U8);
-    micv_shim::check(micv_generate_edge_host(micv_shim::context(), input.ptr<uint8_t>(), input.rows, input.cols,
-                                             input.step, gaussianSize, gaussianSigma, lowerThreshold,
-                                             upperThreshold, out.ptr<uint8_t>(), out.step));
+    if (input.type() == micv_shim::U8)
+        micv_shim::check(micv_generate_edge_host(micv_shim::context(), input.ptr<uint8_t>(), input.rows, input.cols,
+                                                 input.step, gaussianSize, gaussianSigma, lowerThreshold,
+                                                 upperThreshold, out.ptr<uint8_t>(), out.step));
+    else
+        micv_shim::check(micv_generate_edge_f32_host(micv_shim::context(), input.ptr<float>(), input.rows, input.cols,
+                                                     input.step, gaussianSize, gaussianSigma, lowerThreshold,
+                                                     upperThreshold, out.ptr<uint8_t>(), out.step));
+    output = out;
+}
+// sol::gaussianBlur, Solution.h:21, Solution.cpp:49-61: the output has the input's type (CV_8UC1 or CV_32FC1)
+inline void gaussianBlur(const Mat &input, const int gaussianSize, const double gaussianSigma, Mat &output) {
+    micv_shim::require(input.type() == micv_shim::U8 || input.type() == micv_shim::F32,
+                       "sol::gaussianBlur: CV_8UC1 or CV_32FC1 expected");
+    Mat out(input.rows, input.cols, input.type());
+    if (input.type() == micv_shim::U8)
+        micv_shim::check(micv_gaussian_blur_u8_host(micv_shim::context(), input.ptr<uint8_t>(), input.rows, input.cols,
+                                                    input.step, gaussianSize, gaussianSigma, out.ptr<uint8_t>(), out.step));
+    else
+        micv_shim::check(micv_gaussian_blur_f32_host(micv_shim::context(), input.ptr<float>(), input.rows, input.cols,
+                                                     input.step, gaussianSize, gaussianSigma, out.ptr<float>(), out.step));
+    output = out;
+}
+// Solution.h:26-30, :39-41, Solution.cpp:63-79
+inline void houghLinesAccumulate(const Mat &edgeMask, const unsigned int rhoBinSize, const unsigned int thetaBinSize,
+                                 Mat &accumulator) {
+    cuda::houghLinesAccumulate(edgeMask, rhoBinSize, thetaBinSize, accumulator);
+}
+inline void houghCirclesAccumulate(const Mat &edgeMask, const size_t radius, Mat &accumulator) {
+    cuda::houghCirclesAccumulate(edgeMask, radius, accumulator);
+}
+inline void findLocalMaxima(const Mat &accumulator, const unsigned int numPeaks, const int threshold,
+                            std::vector<std::pair<unsigned int, unsigned int>> &localMaxima) {
+    cuda::findLocalMaxima(accumulator, numPeaks, threshold, localMaxima);
+}
+// The radius loops of main.cpp:173-180, :263-270, :299-307 as one call (micv_hough_circles_range_peaks_host): entry i of
+// localMaxima holds what houghCirclesAccumulate(edgeMask, minRadius + i) + findLocalMaxima(numPeaks, threshold) give.
+inline void houghCirclesSearch(const Mat &edgeMask, const size_t minRadius, const size_t maxRadius,
+                               const unsigned int numPeaks, const int threshold,
+                               std::vector<std::vector<std::pair<unsigned int, unsigned int>>> &localMaxima) {
+    micv_shim::require(edgeMask.type() == micv_shim::U8, "sol::houghCirclesSearch: CV_8UC1 expected");
+    localMaxima.clear();
+    if (minRadius > maxRadius) return;
+    micv_shim::require(maxRadius <= 0xFFFFFFFFull, "sol::houghCirclesSearch: radius out of range");
+    const size_t n = maxRadius - minRadius + 1;
+    std::vector<uint32_t> peaks(n * numPeaks * 2 + 2);
+    std::vector<int64_t> counts(n);
+    micv_shim::check(micv_hough_circles_range_peaks_host(micv_shim::context(), edgeMask.ptr<uint8_t>(), edgeMask.rows,
+                                                         edgeMask.cols, edgeMask.step, (unsigned)minRadius,
+                                                         (unsigned)maxRadius, numPeaks, threshold, peaks.data(),
+                                                         counts.data(), nullptr));
+    localMaxima.resize(n);
+    for (size_t i = 0; i < n; i++)
+        for (int64_t k = 0; k < counts[i]; k++)
+            localMaxima[i].emplace_back(peaks[(i * numPeaks + k) * 2], peaks[(i * numPeaks + k) * 2 + 1]);
+}
+// sol::rowColToRhoTheta, Solution.h:56-58, Solution.cpp:81-89
+inline std::pair<int, int> rowColToRhoTheta(const std::pair<unsigned int, unsigned int> &coordinates,
+                                            const Mat &inputImage, const unsigned int rhoBinSize,
+                                            const unsigned int thetaBinSize) {
+    const size_t diagDist = (size_t)std::ceil(std::sqrt((double)(inputImage.rows * inputImage.rows + inputImage.cols * inputImage.cols)));
+    const int rho = (int)((size_t)coordinates.first * rhoBinSize - diagDist);
+    const int theta = (int)(coordinates.second * thetaBinSize + (unsigned)-90);
+    return std::make_pair(rho, theta);
+}
+namespace detail {
+inline void require_bgr(const Mat &image, const char *what) {
+    micv_shim::require(image.depth() == micv_shim::U8 && image.channels() == 3, what);
+}
+inline void color_bytes(const micv_shim::Scalar &color, uint8_t *c) {  // saturate_cast<uchar> of the first three entries
+    for (int i = 0; i < 3; i++) {
+        const double v = color.val[i];
+        const long r = v >= -2147483648.0 && v < 2147483648.0 ? std::lrint(v) : -1;
+        c[i] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
+    }
+}
+}  // namespace detail
+// sol::drawLinesParametric, Solution.h:62-64, Solution.cpp:117-123, on an 8-bit three-channel image (GRAY2RGB first, as
+// the driver does).  (rho, theta) pairs of rowColToRhoTheta are (row - diag, col - 90) at bin size 1, which is how they
+// are handed to micv_draw_lines_parametric_host; theta outside [-90, 89] or rho < -diag name no accumulator cell and
+// are not drawn.
+inline void drawLinesParametric(Mat &image, const std::vector<std::pair<int, int>> &rhoTheta,
+                                const micv_shim::Scalar color) {
+    detail::require_bgr(image, "sol::drawLinesParametric: CV_8UC3 expected");
+    const long long diag = (long long)std::ceil(std::sqrt((double)(image.rows * image.rows + image.cols * image.cols)));
+    std::vector<uint32_t> peaks;
+    for (const auto &val : rhoTheta) {
+        if (val.second < -90 || val.second > 89 || (long long)val.first + diag < 0) continue;
+        peaks.push_back((uint32_t)((long long)val.first + diag));
+        peaks.push_back((uint32_t)(val.second + 90));
+    }
+    uint8_t c[3];
+    detail::color_bytes(color, c);
+    for (size_t at = 0; at < peaks.size() / 2; at += 4096) {  // the entry takes up to 4096 lines
+        const int64_t n = (int64_t)std::min<size_t>(4096, peaks.size() / 2 - at);
+        micv_shim::check(micv_draw_lines_parametric_host(micv_shim::context(), image.ptr<uint8_t>(), image.rows, image.cols,
+                                                         image.step, peaks.data() + 2 * at, n, 1, 1, c));
+    }
+}
+// sol::drawLineParametric, Solution.h:59, Solution.cpp:91-115 (integer-valued rho and theta, as the driver passes them)
+inline void drawLineParametric(Mat &image, const float rho, const float theta, const micv_shim::Scalar color) {
+    micv_shim::require(rho == std::nearbyint(rho) && theta == std::nearbyint(theta) && std::fabs(rho) < 1e9f,
+                       "sol::drawLineParametric: integer-valued rho and theta expected");
+    drawLinesParametric(image, {std::make_pair((int)rho, (int)theta)}, color);
+}
+// sol::drawCircles, Solution.h:67-70, Solution.cpp:125-132
+inline void drawCircles(Mat &image, const std::vector<std::pair<unsigned int, unsigned int>> &center,
+                        const size_t radius, const micv_shim::Scalar color) {
+    detail::require_bgr(image, "sol::drawCircles: CV_8UC3 expected");
+    micv_shim::require(radius <= 0xFFFFFFFFull, "sol::drawCircles: radius out of range");
+    uint8_t c[3];
+    detail::color_bytes(color, c);
+    std::vector<uint32_t> peaks;
+    for (const auto &p : center) {
+        peaks.push_back(p.first);
+        peaks.push_back(p.second);
+    }
+    for (size_t at = 0; at < center.size(); at += 4096) {
+        const int64_t n = (int64_t)std::min<size_t>(4096, center.size() - at);
+        micv_shim::check(micv_draw_circles_host(micv_shim::context(), image.ptr<uint8_t>(), image.rows, image.cols, image.step,
+                                                peaks.data() + 2 * at, &n, 1, (unsigned)n, (unsigned)radius, c));
+    }
+}
+// drawCircles for the lists of houghCirclesSearch: entry i with radius minRadius + i, all in one call
+inline void drawCircles(Mat &image, const std::vector<std::vector<std::pair<unsigned int, unsigned int>>> &centers,
+                        const size_t minRadius, const micv_shim::Scalar color) {
+    detail::require_bgr(image, "sol::drawCircles: CV_8UC3 expected");
+    size_t k = 0;
+    for (const auto &l : centers) k = std::max(k, l.size());
+    micv_shim::require(k <= 4096 && minRadius + centers.size() <= 0xFFFFFFFFull, "sol::drawCircles: too many circles");
+    if (k == 0) return;
+    std::vector<uint32_t> peaks(centers.size() * k * 2, 0);
+    std::vector<int64_t> counts(centers.size());
+    for (size_t i = 0; i < centers.size(); i++) {
+        counts[i] = (int64_t)centers[i].size();
+        for (size_t j = 0; j < centers[i].size(); j++) {
+            peaks[(i * k + j) * 2] = centers[i][j].first;
+            peaks[(i * k + j) * 2 + 1] = centers[i][j].second;
+        }
+    }
+    uint8_t c[3];
+    detail::color_bytes(color, c);
+    micv_shim::check(micv_draw_circles_host(micv_shim::context(), image.ptr<uint8_t>(), image.rows, image.cols, image.step,
+                                            peaks.data(), counts.data(), (unsigned)centers.size(), (unsigned)k,
+                                            (unsigned)minRadius, c));
+}
+// sol::findParallelLines, Solution.h:72-75, Solution.cpp:134-173.  The kept pairs come in INPUT order (the reference's
+// order is that of an unordered_multimap's buckets; every use draws them in one colour).
+inline void findParallelLines(const std::vector<std::pair<uint32_t, uint32_t>> &rhoTheta, const size_t deltaTheta,
+                              const size_t deltaRho, std::vector<std::pair<uint32_t, uint32_t>> &parallelRhoThetas) {
+    parallelRhoThetas.clear();
+    micv_shim::require(rhoTheta.size() <= 4096, "sol::findParallelLines: at most 4096 lines");
+    micv_shim::require(deltaTheta >= 1 && deltaRho >= 1 && deltaTheta <= 0xFFFFFFFFull && deltaRho <= 0xFFFFFFFFull,
+                       "sol::findParallelLines: deltaTheta and deltaRho must be positive");
+    std::vector<uint32_t> in, out(rhoTheta.size() * 2 + 2);
+    for (const auto &p : rhoTheta) {
+        in.push_back(p.first);
+        in.push_back(p.second);
+    }
+    int64_t n = 0;
+    micv_shim::check(micv_parallel_lines_host(micv_shim::context(), in.data(), (int64_t)rhoTheta.size(), (unsigned)deltaRho,
+                                              (unsigned)deltaTheta, out.data(), &n));
+    for (int64_t i = 0; i < n; i++) parallelRhoThetas.emplace_back(out[2 * i], out[2 * i + 1]);
+}
+// cv::erode(src, dst, cv::getStructuringElement(cv::MORPH_ELLIPSE, cv::Size(ksize, ksize))), main.cpp:246-248
+inline void erodeEllipse(const Mat &input, const int ksize, Mat &output) {
+    micv_shim::require(input.type() == micv_shim::U8 || input.type() == micv_shim::F32, "sol::erodeEllipse: CV_8UC1 or CV_32FC1 expected");
+    Mat out(input.rows, input.cols, input.type());
+    if (input.type() == micv_shim::U8)
+        micv_shim::check(micv_erode_ellipse_u8_host(micv_shim::context(), input.ptr<uint8_t>(), input.rows, input.cols, input.step,
+                                                    ksize, out.ptr<uint8_t>(), out.step));
+    else
+        micv_shim::check(micv_erode_ellipse_f32_host(micv_shim::context(), input.ptr<float>(), input.rows, input.cols, input.step,
+                                                     ksize, out.ptr<float>(), out.step));
+    output = out;
+}
+// cv::cvtColor(src, dst, CV_GRAY2RGB) to 8 bit (main.cpp:88): CV_8UC1 or CV_32FC1 -> CV_8UC3
+inline void gray2rgb(const Mat &input, Mat &output) {
+    micv_shim::require(input.type() == micv_shim::U8 || input.type() == micv_shim::F32, "sol::gray2rgb: CV_8UC1 or CV_32FC1 expected");
+    Mat out(input.rows, input.cols, micv_shim::U8C3);
+    micv_shim::check(micv_gray_to_rgb8_host(micv_shim::context(), input.data, input.type() == micv_shim::U8 ? MICV_DEPTH_8U : MICV_DEPTH_32F,
+                                            input.rows, input.cols, input.step, out.ptr<uint8_t>(), out.step));
     output = out;
 }
 // The matching step of Solution::siftHelper, ps4_cpp/src/Solution.cpp:172-184:
