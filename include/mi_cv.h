@@ -1215,6 +1215,82 @@ int micv_geom_trial_indices(micv_ransac_rng *rng, int64_t n, int trials, int32_t
 int micv_geom_sample_indices_dev(micv_ctx *ctx, uint64_t seed, int n, int count, int64_t T, int32_t *out,
                                  micv_stream stream);
 
+/* ------------------------------------------------------------------ ps5: driver ------ */
+/* What ProblemSets/ps5_cpp/src/Solution.cpp does around lk:: and pyr::, on the device: every runProblem* of ps5 runs
+ * from the uploaded frames to the images it would write without a host synchronisation.  The drawing and the montage
+ * follow shim/micv_viz.hpp (drawVelocityVectors, arrowed_line, line, savePyramid), which restates OpenCV 3.4.1's
+ * cv::arrowedLine / cv::LineIterator / cv::resize(INTER_NEAREST) / cv::normalize, PARITY UNPINNED;
+ * the `_dev` forms equal those host loops byte for byte (see DESIGN.md for the one condition, a tip point within an ulp
+ * of a rounding tie, which no lattice point can meet).  Every `_dev` entry is asynchronous on `stream`; every `_host`
+ * entry uploads, runs the same kernels and downloads. */
+
+/* drawVelocityVectors (Solution.cpp:13-37): on `batch` 8-bit 3-channel interleaved images (image i at img + i*img_pitch,
+ * rows `stride` bytes apart), drawn on in place, the arrows (x, y) -> (x + u, y + v) at the lattice points
+ * y = 0, max(1, rows/30), ..., x = 0, max(1, cols/30), ... of field i (u + i*field_pitch bytes, rows `fstride` bytes
+ * apart).  A lattice point whose u or v is not finite or exceeds 1e6 in magnitude draws nothing.  End points are lrint of
+ * the float32 sums; tip length, angle and tip points in double; every stroke is cv::LineIterator's walk, each pixel
+ * bounds-checked.  color: 3 bytes, stored as they are.  rows, cols <= 32767; batch <= 65535. */
+int micv_draw_velocity_vectors_dev(micv_ctx *ctx, uint8_t *img, size_t img_pitch, size_t stride, const float *u, const float *v,
+                                   size_t field_pitch, size_t fstride, int batch, int rows, int cols, const uint8_t *color,
+                                   micv_stream stream);
+int micv_draw_velocity_vectors_host(micv_ctx *ctx, uint8_t *img, size_t img_pitch, size_t stride, const float *u, const float *v,
+                                    size_t field_pitch, size_t fstride, int batch, int rows, int cols, const uint8_t *color);
+/* prevImg.clone() and, for a grey frame, cv::cvtColor(GRAY2RGB) (Solution.cpp:66, :17-19): the 3-channel image the
+ * arrows are drawn on, so that they never touch the caller's frame.  depth MICV_DEPTH_8U and 1 or 3 channels; anything
+ * else is MICV_EINVAL (micv_viz::drawVelocityVectors requires 8 bit as well). */
+int micv_gray_or_bgr_to_bgr8_dev(micv_ctx *ctx, const void *src, int depth, int channels, int rows, int cols, size_t sstride,
+                                 uint8_t *dst, size_t dstride, micv_stream stream);
+int micv_gray_or_bgr_to_bgr8_host(micv_ctx *ctx, const void *src, int depth, int channels, int rows, int cols, size_t sstride,
+                                  uint8_t *dst, size_t dstride);
+/* savePyramid (Solution.cpp:86-99): levels[0..3] with the sizes the caller gives (level 0 is R x C; the others need not
+ * be R >> l), depth MICV_DEPTH_32F or MICV_DEPTH_8U, into one 2R x 2C 8-bit image, level k at tile (k / 2, k % 2).
+ * 32F levels are normalised first, each by its own range, with the arithmetic of micv_normalize_minmax_* (NaNs are
+ * ignored by the range and give 0; a range <= DBL_EPSILON gives scale 0); a tile pixel (y, x) shows the level's pixel
+ * (min((int)floor(y * ((double)rows_k / R)), rows_k - 1), likewise x): cv::resize(INTER_NEAREST).  Two launches (the
+ * four ranges, the montage); one for 8U.  With micv_laplacian_pyramid_dev in front this is ps5-2-b-1.  Level sizes up
+ * to 16383. */
+int micv_pyramid_montage_dev(micv_ctx *ctx, const void *const *levels, const int *level_rows, const int *level_cols,
+                             const size_t *level_strides, int depth, uint8_t *dst, size_t dstride, micv_stream stream);
+int micv_pyramid_montage_host(micv_ctx *ctx, const void *const *levels, const int *level_rows, const int *level_cols,
+                              const size_t *level_strides, int depth, uint8_t *dst, size_t dstride);
+/* warpHelper's `prev - warped` (Solution.cpp:118-123) in one kernel: diff = prev - remap(next, x + du, y + dv) with
+ * micv_lk_warp_dev's sample (taps, border, rounding), then one unfused f32 subtraction: bit-identical to
+ * micv_lk_warp_dev followed by a subtraction.  diff must not alias an input (MICV_EINVAL). */
+int micv_lk_warp_diff_dev(micv_ctx *ctx, const float *prev, size_t pstride, const float *next, size_t nstride, const float *du,
+                          const float *dv, size_t fstride, int rows, int cols, float *diff, size_t dstride, micv_stream stream);
+int micv_lk_warp_diff_host(micv_ctx *ctx, const float *prev, size_t pstride, const float *next, size_t nstride, const float *du,
+                           const float *dv, size_t fstride, int rows, int cols, float *diff, size_t dstride);
+/* warpHelper (Solution.cpp:101-128) over `nframes` grey f32 images of one size (frame t at frames + t*frame_pitch
+ * bytes: one pyramid level of every frame, as micv_gaussian_pyramid_batch_dev lays it out): for every consecutive pair
+ * (t - 1, t) micv_lk_flow_dev(prev, next, win) and the fused warp-diff with that flow, then ONE batched min-max
+ * normalisation of the nframes - 1 differences to 8 bit (pair p at diff_u8 + p*u8_pitch).  diff_f32, u, v: optional
+ * (NULL = not wanted) dense outputs, pair p at + p*rows*cols floats.  Temporaries come from the context. */
+int micv_ps5_warp_diff_seq_dev(micv_ctx *ctx, const float *frames, size_t frame_pitch, int nframes, int rows, int cols,
+                               size_t stride, int win, uint8_t *diff_u8, size_t u8_pitch, size_t u8_stride, float *diff_f32,
+                               float *u, float *v, micv_stream stream);
+/* The host form takes the frames as micv_lk_flow_seq_host does (nframes host images of one format: 1 / 3 / 4 channels,
+ * 8U or 32F) plus the pyramid level: grey conversion and micv_gaussian_pyramid_batch_dev on the device, then the chain
+ * on level `level` of `levels`.  Outputs are (rows >> level) x (cols >> level), dense, pair after pair. */
+int micv_ps5_warp_diff_seq_host(micv_ctx *ctx, const void *const *frames, int nframes, int rows, int cols, size_t stride,
+                                int channels, int depth, int levels, int level, int win, uint8_t *diff_u8, float *diff_f32,
+                                float *u, float *v);
+/* One denseLKWrapper (Solution.cpp:40-84) as one call: two 8-bit frames of 1 or 3 channels -> grey conversion
+ * (micv_to_gray_f32_dev: naive mode converts first, :48-61; pyramidal mode hands the frames to the chain, which converts
+ * them the same way, as micv_lk_flow_pyr_frames_host), the flow (micv_lk_flow_dev, or micv_lk_flow_pyr_dev with `levels`),
+ * the arrows on a copy of `prev` (the two entries above), and, when jet_u / jet_v are given, the JET maps of the
+ * normalised u and v: one micv_normalize_minmax_batch_dev of two where v lies behind u and jet_v behind jet_u in memory
+ * (allocate each pair as one block), otherwise one micv_normalize_minmax_dev per field, with the same bytes.  The
+ * caller's frames are not written. */
+#define MICV_LK_NAIVE     0 /* LKMode::NAIVE */
+#define MICV_LK_PYRAMIDAL 1 /* LKMode::HEIRARCHICAL (sic) */
+int micv_dense_lk_display_dev(micv_ctx *ctx, const void *prev, const void *next, int rows, int cols, size_t stride, int channels,
+                              int depth, int mode, int win, int levels, const uint8_t *color, float *u, float *v, size_t ostride,
+                              uint8_t *arrows, size_t astride, uint8_t *jet_u, uint8_t *jet_v, size_t jstride,
+                              micv_stream stream);
+int micv_dense_lk_display_host(micv_ctx *ctx, const void *prev, const void *next, int rows, int cols, size_t stride, int channels,
+                               int depth, int mode, int win, int levels, const uint8_t *color, float *u, float *v, size_t ostride,
+                               uint8_t *arrows, size_t astride, uint8_t *jet_u, uint8_t *jet_v, size_t jstride);
+
 #ifdef __cplusplus
 }
 #endif

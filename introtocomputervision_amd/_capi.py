@@ -40,6 +40,7 @@ KNN_MAX_DIMS, KNN_MAX_K, KNN_MAX_LABELS, KNN_MAX_GROUPS = 64, 32, 16, 32
 GEOM_F64 = 1  # ps3 (mi_cv.h): geometry
 DEPTH_8U, DEPTH_8S, DEPTH_32F = 0, 1, 5  # mi_cv.h
 DISPARITY_SSD, DISPARITY_NCC = 0, 1  # display (mi_cv.h)
+LK_NAIVE, LK_PYRAMIDAL = 0, 1  # ps5 driver (mi_cv.h)
 WARP_INVERSE_MAP, WARP_NEAREST = 16, 1  # ps4 registration (mi_cv.h)
 # micv_ctx_set_option (include/mi_cv.h): none of these changes a result
 (OPT_LK_STREAM_GROUPS, OPT_LK_FORCE_GENERIC, OPT_LK_NARROW_TILES, OPT_SOBEL_GENERIC, OPT_HARRIS_GENERIC,
@@ -177,6 +178,19 @@ SIGNATURES = {
     "micv_draw_lines_parametric_host": (i32, [vp, vp, i32, i32, sz, vp, i64, u32, u32, vp]),
     "micv_draw_circles_dev": (i32, [vp, vp, i32, i32, sz, vp, vp, u32, u32, u32, vp, vp]),
     "micv_draw_circles_host": (i32, [vp, vp, i32, i32, sz, vp, vp, u32, u32, u32, vp]),
+    # ps5 driver
+    "micv_draw_velocity_vectors_dev": (i32, [vp, vp, sz, sz, vp, vp, sz, sz, i32, i32, i32, vp, vp]),
+    "micv_draw_velocity_vectors_host": (i32, [vp, vp, sz, sz, vp, vp, sz, sz, i32, i32, i32, vp]),
+    "micv_gray_or_bgr_to_bgr8_dev": (i32, [vp, vp, i32, i32, i32, i32, sz, vp, sz, vp]),
+    "micv_gray_or_bgr_to_bgr8_host": (i32, [vp, vp, i32, i32, i32, i32, sz, vp, sz]),
+    "micv_pyramid_montage_dev": (i32, [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(sz), i32, vp, sz, vp]),
+    "micv_pyramid_montage_host": (i32, [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(sz), i32, vp, sz]),
+    "micv_lk_warp_diff_dev": (i32, [vp, vp, sz, vp, sz, vp, vp, sz, i32, i32, vp, sz, vp]),
+    "micv_lk_warp_diff_host": (i32, [vp, vp, sz, vp, sz, vp, vp, sz, i32, i32, vp, sz]),
+    "micv_ps5_warp_diff_seq_dev": (i32, [vp, vp, sz, i32, i32, i32, sz, i32, vp, sz, sz, vp, vp, vp, vp]),
+    "micv_ps5_warp_diff_seq_host": (i32, [vp, C.POINTER(vp), i32, i32, i32, sz, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "micv_dense_lk_display_dev": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp, vp, sz, vp]),
+    "micv_dense_lk_display_host": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp, vp, sz]),
     # ps4 matching
     "micv_bf_knn2_dev": (i32, [vp, vp, i32, sz, vp, i32, sz, i32, vp, vp, vp]),
     "micv_bf_ratio_filter_dev": (i32, [vp, vp, vp, i32, f64, vp, vp, i64, vp, vp]),

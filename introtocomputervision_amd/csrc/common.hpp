@@ -162,6 +162,11 @@ struct micv_ctx {
     int prof_end(int level, hipStream_t s);
     // Returns scratch of at least `bytes` (256-B aligned). Growing synchronises the device.
     int reserve(size_t bytes, void **out);
+    // A second block with the same rules, for the temporaries of a chain whose steps are entry points that carve the
+    // arena themselves (ps5.hip: the flows and differences around micv_lk_flow_dev).
+    void *chain_pool = nullptr;
+    size_t chain_pool_bytes = 0;
+    int reserve_chain(size_t bytes, void **out);
 };
 
 namespace micv {

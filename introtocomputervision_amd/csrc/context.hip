@@ -90,6 +90,21 @@ int micv_ctx::reserve(size_t bytes, void **out) {
     return MICV_OK;
 }
 
+int micv_ctx::reserve_chain(size_t bytes, void **out) {
+    if (bytes > chain_pool_bytes) {
+        MICV_HIP(hipSetDevice(device));
+        MICV_HIP(hipDeviceSynchronize());
+        if (chain_pool) MICV_HIP(hipFree(chain_pool));
+        chain_pool = nullptr;
+        chain_pool_bytes = 0;
+        const size_t want = (bytes + (size_t(1) << 20) - 1) & ~((size_t(1) << 20) - 1);
+        MICV_HIP(hipMalloc(&chain_pool, want));
+        chain_pool_bytes = want;
+    }
+    *out = chain_pool;
+    return MICV_OK;
+}
+
 int micv_ctx::stereo_flag_word(unsigned **out) {
     if (!stereo_flag) {
         void *p = nullptr;
@@ -255,6 +270,7 @@ void micv_ctx_destroy(micv_ctx *ctx) {
     for (void *t : ctx->trig_tables)
         if (t) (void)hipFree(t);
     if (ctx->arena) (void)hipFree(ctx->arena);
+    if (ctx->chain_pool) (void)hipFree(ctx->chain_pool);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     delete ctx;
 }

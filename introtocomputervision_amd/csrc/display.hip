@@ -22,6 +22,7 @@
 
 #include "common.hpp"
 #include "cv_rng.hpp"
+#include "minmax_keys.hpp"
 
 namespace micv {
 
@@ -44,13 +45,6 @@ constexpr int kThreads = 256;
 constexpr int kTileW = 128, kTileH = 8;  // apply: 32 lanes x 4 pixels, 8 rows
 constexpr int kKeySlots = micv_ctx::kDisplayKeySlots, kKeyStride = micv_ctx::kDisplayKeyStride;  // (stride in words)
 constexpr unsigned kMaxBlocksPerImage = 512;  // 32 workgroups, 64 atomics, per line
-
-// float <-> unsigned, order-preserving (-inf < ... < -0 < +0 < ... < +inf); no non-NaN float maps to 0 or to ~0.
-__device__ __forceinline__ unsigned key_of(float v) {
-    const unsigned u = __float_as_uint(v);
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float value_of(unsigned k) { return __uint_as_float((k >> 31) ? k ^ 0x80000000u : ~k); }
 
 struct MinMaxArgs {
     const void *src;   // image z at src + z * pitch

@@ -1467,4 +1467,168 @@ int micv_draw_circles_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, size
     return MICV_OK;
 }
 
+// ---- ps5 driver (ps5.hip) ----------------------------------------------------------------------
+
+int micv_draw_velocity_vectors_host(micv_ctx *ctx, uint8_t *img, size_t img_pitch, size_t stride, const float *u, const float *v,
+                                    size_t field_pitch, size_t fstride, int batch, int rows, int cols, const uint8_t *color) {
+    HOST_PROLOGUE("micv_draw_velocity_vectors_host");
+    MICV_REQUIRE(img && u && v && color && rows > 0 && cols > 0 && batch >= 0 && stride >= (size_t)cols * 3 && stride_ok(fstride, cols, 4),
+                 "micv_draw_velocity_vectors_host: bad argument, size %dx%d or stride", rows, cols);
+    MICV_REQUIRE(batch <= 1 || (img_pitch >= (size_t)(rows - 1) * stride + (size_t)cols * 3 &&
+                                field_pitch >= (size_t)(rows - 1) * fstride + (size_t)cols * 4),
+                 "micv_draw_velocity_vectors_host: a pitch is smaller than an image or a field");
+    if (batch == 0) return MICV_OK;
+    const size_t irb = (size_t)cols * 3, frb = (size_t)cols * 4, ip = pitch256(irb * rows), fp = pitch256(frb * rows), nb = (size_t)batch;
+    DevBuf di(ip * nb), du(fp * nb), dv(fp * nb);
+    MICV_ALLOC_OK(di); MICV_ALLOC_OK(du); MICV_ALLOC_OK(dv);
+    for (size_t i = 0; i < nb; i++) {
+        MICV_TRY(up2d(di.as<char>() + i * ip, img + i * img_pitch, stride, irb, rows, s));
+        MICV_TRY(up2d(du.as<char>() + i * fp, reinterpret_cast<const char *>(u) + i * field_pitch, fstride, frb, rows, s));
+        MICV_TRY(up2d(dv.as<char>() + i * fp, reinterpret_cast<const char *>(v) + i * field_pitch, fstride, frb, rows, s));
+    }
+    MICV_TRY(micv_draw_velocity_vectors_dev(ctx, di.as<uint8_t>(), ip, irb, du.as<float>(), dv.as<float>(), fp, frb, batch, rows, cols,
+                                            color, s));
+    for (size_t i = 0; i < nb; i++) MICV_TRY(down2d(img + i * img_pitch, stride, di.as<char>() + i * ip, irb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_gray_or_bgr_to_bgr8_host(micv_ctx *ctx, const void *src, int depth, int channels, int rows, int cols, size_t sstride,
+                                  uint8_t *dst, size_t dstride) {
+    MICV_REQUIRE(depth == MICV_DEPTH_8U && (channels == 1 || channels == 3),
+                 "micv_gray_or_bgr_to_bgr8_host: depth %d / %d channels not supported (8U, 1 or 3 channels)", depth, channels);
+    PS1_IMAGE_HOST("micv_gray_or_bgr_to_bgr8_host", src, sstride, (size_t)cols * channels, dst, dstride, (size_t)cols * 3,
+                   micv_gray_or_bgr_to_bgr8_dev(ctx, ds.p, depth, channels, rows, cols, (size_t)cols * channels, dd.as<uint8_t>(),
+                                                (size_t)cols * 3, s));
+}
+
+int micv_pyramid_montage_host(micv_ctx *ctx, const void *const *levels, const int *level_rows, const int *level_cols,
+                              const size_t *level_strides, int depth, uint8_t *dst, size_t dstride) {
+    HOST_PROLOGUE("micv_pyramid_montage_host");
+    MICV_REQUIRE(levels && level_rows && level_cols && level_strides && dst, "micv_pyramid_montage_host: null argument");
+    MICV_REQUIRE(depth == MICV_DEPTH_32F || depth == MICV_DEPTH_8U, "micv_pyramid_montage_host: depth %d not supported (32F, 8U)", depth);
+    const size_t e = depth == MICV_DEPTH_32F ? 4 : 1;
+    size_t off[5] = {0, 0, 0, 0, 0}, rb[4];
+    for (int l = 0; l < 4; l++) {
+        MICV_REQUIRE(levels[l] && level_rows[l] > 0 && level_cols[l] > 0 && level_rows[l] <= 16383 && level_cols[l] <= 16383 &&
+                         stride_ok(level_strides[l], level_cols[l], e),
+                     "micv_pyramid_montage_host: level %d: null, bad size or stride", l);
+        rb[l] = (size_t)level_cols[l] * e;
+        off[l + 1] = off[l] + pitch256(rb[l] * level_rows[l]);
+    }
+    const int R = level_rows[0], C = level_cols[0];
+    MICV_REQUIRE(dstride >= (size_t)2 * C, "micv_pyramid_montage_host: stride %zu does not hold %d columns", dstride, 2 * C);
+    DevBuf dl(off[4]), dd((size_t)4 * R * C);
+    MICV_ALLOC_OK(dl); MICV_ALLOC_OK(dd);
+    const void *dev_levels[4];
+    for (int l = 0; l < 4; l++) {
+        MICV_TRY(up2d(dl.as<char>() + off[l], levels[l], level_strides[l], rb[l], level_rows[l], s));
+        dev_levels[l] = dl.as<char>() + off[l];
+    }
+    MICV_TRY(micv_pyramid_montage_dev(ctx, dev_levels, level_rows, level_cols, rb, depth, dd.as<uint8_t>(), (size_t)2 * C, s));
+    MICV_TRY(down2d(dst, dstride, dd.p, (size_t)2 * C, 2 * R, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_lk_warp_diff_host(micv_ctx *ctx, const float *prev, size_t pstride, const float *next, size_t nstride, const float *du,
+                           const float *dv, size_t fstride, int rows, int cols, float *diff, size_t dstride) {
+    HOST_PROLOGUE("micv_lk_warp_diff_host");
+    MICV_REQUIRE(prev && next && du && dv && diff && rows > 0 && cols > 0, "micv_lk_warp_diff_host: bad argument");
+    MICV_REQUIRE(stride_ok(pstride, cols, 4) && stride_ok(nstride, cols, 4) && stride_ok(fstride, cols, 4) && stride_ok(dstride, cols, 4),
+                 "micv_lk_warp_diff_host: bad stride");
+    const size_t rb = (size_t)cols * 4, n = rb * rows;
+    DevBuf dp(n), dn(n), dU(n), dV(n), dd(n);
+    MICV_ALLOC_OK(dp); MICV_ALLOC_OK(dn); MICV_ALLOC_OK(dU); MICV_ALLOC_OK(dV); MICV_ALLOC_OK(dd);
+    MICV_TRY(up2d(dp.p, prev, pstride, rb, rows, s));
+    MICV_TRY(up2d(dn.p, next, nstride, rb, rows, s));
+    MICV_TRY(up2d(dU.p, du, fstride, rb, rows, s));
+    MICV_TRY(up2d(dV.p, dv, fstride, rb, rows, s));
+    MICV_TRY(micv_lk_warp_diff_dev(ctx, dp.as<float>(), rb, dn.as<float>(), rb, dU.as<float>(), dV.as<float>(), rb, rows, cols,
+                                   dd.as<float>(), rb, s));
+    MICV_TRY(down2d(diff, dstride, dd.p, rb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_ps5_warp_diff_seq_host(micv_ctx *ctx, const void *const *frames, int nframes, int rows, int cols, size_t stride,
+                                int channels, int depth, int levels, int level, int win, uint8_t *diff_u8, float *diff_f32,
+                                float *u, float *v) {
+    HOST_PROLOGUE("micv_ps5_warp_diff_seq_host");
+    MICV_REQUIRE(frames && diff_u8 && rows > 0 && cols > 0, "micv_ps5_warp_diff_seq_host: bad argument");
+    MICV_REQUIRE(nframes >= 2 && nframes <= 1025, "micv_ps5_warp_diff_seq_host: %d frames (2..1025: at least one pair)", nframes);
+    MICV_REQUIRE((channels == 1 || channels == 3 || channels == 4) && (depth == MICV_DEPTH_8U || depth == MICV_DEPTH_32F),
+                 "micv_ps5_warp_diff_seq_host: frames must be 1/3/4-channel 8U or 32F");
+    MICV_REQUIRE(levels >= 1 && levels <= 16 && level >= 0 && level < levels && (rows >> level) > 0 && (cols >> level) > 0,
+                 "micv_ps5_warp_diff_seq_host: level %d of %d does not fit a %dx%d image", level, levels, rows, cols);
+    MICV_REQUIRE((u == nullptr) == (v == nullptr), "micv_ps5_warp_diff_seq_host: give both flow outputs or none");
+    const size_t es = depth == MICV_DEPTH_8U ? 1 : 4, srb = (size_t)cols * channels * es;
+    MICV_REQUIRE(stride >= srb, "micv_ps5_warp_diff_seq_host: bad stride");
+    for (int t = 0; t < nframes; t++) MICV_REQUIRE(frames[t] != nullptr, "micv_ps5_warp_diff_seq_host: frame %d is null", t);
+    const size_t nf = (size_t)nframes, np = nf - 1, rb = (size_t)cols * 4, n0 = (size_t)rows * cols;
+    // the pyramid block holds levels 1.. only (level 0 is `grey` itself), and nothing when the chain takes level 0
+    size_t lvl_off[17] = {0};
+    if (level > 0)
+        for (int l = 1; l < levels; l++) lvl_off[l + 1] = lvl_off[l] + pitch256((size_t)(rows >> l) * (cols >> l) * 4 * nf);
+    const int lr = rows >> level, lc = cols >> level;
+    const size_t ln = (size_t)lr * lc;
+    DevBuf raw(srb * rows), grey(n0 * 4 * nf), pyr(lvl_off[levels] ? lvl_off[levels] : 16), d8(ln * np), df(diff_f32 ? ln * 4 * np : 16),
+        dU(u ? ln * 4 * np : 16), dV(u ? ln * 4 * np : 16);
+    MICV_ALLOC_OK(raw); MICV_ALLOC_OK(grey); MICV_ALLOC_OK(pyr); MICV_ALLOC_OK(d8); MICV_ALLOC_OK(df); MICV_ALLOC_OK(dU); MICV_ALLOC_OK(dV);
+    for (size_t t = 0; t < nf; t++) {  // (one raw block: the copy of frame t + 1 queues behind the conversion of frame t)
+        MICV_TRY(up2d(raw.p, frames[t], stride, srb, rows, s));
+        MICV_TRY(micv_to_gray_f32_dev(ctx, raw.p, rows, cols, srb, channels, depth, grey.as<float>() + t * n0, rb, s));
+    }
+    const float *lvl_frames = grey.as<float>();
+    if (level > 0) {
+        float *dst_levels[16];
+        for (int l = 0; l < levels; l++) dst_levels[l] = l == 0 ? nullptr : reinterpret_cast<float *>(pyr.as<char>() + lvl_off[l]);
+        MICV_TRY(micv_gaussian_pyramid_batch_dev(ctx, grey.as<float>(), nframes, n0 * 4, rows, cols, rb, levels, dst_levels, nullptr,
+                                                 nullptr, s));
+        lvl_frames = dst_levels[level];
+    }
+    MICV_TRY(micv_ps5_warp_diff_seq_dev(ctx, lvl_frames, ln * 4, nframes, lr, lc, (size_t)lc * 4, win, d8.as<uint8_t>(), ln, (size_t)lc,
+                                        diff_f32 ? df.as<float>() : nullptr, u ? dU.as<float>() : nullptr, u ? dV.as<float>() : nullptr,
+                                        s));
+    MICV_HIP(hipMemcpyAsync(diff_u8, d8.p, ln * np, hipMemcpyDeviceToHost, s));
+    if (diff_f32) MICV_HIP(hipMemcpyAsync(diff_f32, df.p, ln * 4 * np, hipMemcpyDeviceToHost, s));
+    if (u) {
+        MICV_HIP(hipMemcpyAsync(u, dU.p, ln * 4 * np, hipMemcpyDeviceToHost, s));
+        MICV_HIP(hipMemcpyAsync(v, dV.p, ln * 4 * np, hipMemcpyDeviceToHost, s));
+    }
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_dense_lk_display_host(micv_ctx *ctx, const void *prev, const void *next, int rows, int cols, size_t stride, int channels,
+                               int depth, int mode, int win, int levels, const uint8_t *color, float *u, float *v, size_t ostride,
+                               uint8_t *arrows, size_t astride, uint8_t *jet_u, uint8_t *jet_v, size_t jstride) {
+    HOST_PROLOGUE("micv_dense_lk_display_host");
+    MICV_REQUIRE(prev && next && color && u && v && arrows && rows > 0 && cols > 0, "micv_dense_lk_display_host: bad argument");
+    MICV_REQUIRE(depth == MICV_DEPTH_8U && (channels == 1 || channels == 3),
+                 "micv_dense_lk_display_host: depth %d / %d channels not supported (8-bit frames of 1 or 3 channels)", depth, channels);
+    MICV_REQUIRE((jet_u == nullptr) == (jet_v == nullptr), "micv_dense_lk_display_host: give both colour maps or none");
+    const size_t srb = (size_t)cols * channels, rb = (size_t)cols * 4, n = rb * rows, irb = (size_t)cols * 3, in = pitch256(irb * rows);
+    MICV_REQUIRE(stride >= srb && stride_ok(ostride, cols, 4) && astride >= irb && (!jet_u || jstride >= irb),
+                 "micv_dense_lk_display_host: bad stride");
+    const size_t fn = pitch256(n);
+    DevBuf dp(srb * rows), dn(srb * rows), duv(2 * fn), da(in), dj(jet_u ? 2 * in : 16);
+    MICV_ALLOC_OK(dp); MICV_ALLOC_OK(dn); MICV_ALLOC_OK(duv); MICV_ALLOC_OK(da); MICV_ALLOC_OK(dj);
+    MICV_TRY(up2d(dp.p, prev, stride, srb, rows, s));
+    MICV_TRY(up2d(dn.p, next, stride, srb, rows, s));
+    float *du = duv.as<float>(), *dv = reinterpret_cast<float *>(duv.as<char>() + fn);
+    uint8_t *ju = jet_u ? dj.as<uint8_t>() : nullptr, *jv = jet_u ? ju + in : nullptr;
+    MICV_TRY(micv_dense_lk_display_dev(ctx, dp.p, dn.p, rows, cols, srb, channels, depth, mode, win, levels, color, du, dv, rb,
+                                       da.as<uint8_t>(), irb, ju, jv, irb, s));
+    MICV_TRY(down2d(u, ostride, du, rb, rows, s));
+    MICV_TRY(down2d(v, ostride, dv, rb, rows, s));
+    MICV_TRY(down2d(arrows, astride, da.p, irb, rows, s));
+    if (jet_u) {
+        MICV_TRY(down2d(jet_u, jstride, ju, irb, rows, s));
+        MICV_TRY(down2d(jet_v, jstride, jv, irb, rows, s));
+    }
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
 }  // extern "C"

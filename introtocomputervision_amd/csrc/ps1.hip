@@ -8,6 +8,7 @@
 #include <cmath>
 #include <type_traits>
 
+#include "draw.hpp"
 #include "kernels.hpp"
 
 namespace micv {
@@ -165,18 +166,10 @@ __global__ __launch_bounds__(1024) void parallel_lines_kernel(const uint32_t *__
 // ---- sol::drawLinesParametric.  blockIdx.y = the peak; a thread is one step along the segment's major axis, and only
 // the steps whose major coordinate lies inside the image are dealt out (the end points of a near-vertical line lie up to
 // ~115 image diagonals outside).  After i major steps of micv_viz::line's walk the minor coordinate has advanced
-// m(i) = (2 minor i + major - 1) div (2 major).
+// m(i) = (2 minor i + major - 1) div (2 major) (draw.hpp).
 struct LineTrig {
     float c[180], s[180];  // cos / sin of the float radian of theta = -90 + i
 };
-__device__ __forceinline__ void put_rgb(uint8_t *img, size_t stride, int rows, int cols, long long x, long long y, uint8_t c0,
-                                        uint8_t c1, uint8_t c2) {
-    if (x < 0 || x >= cols || y < 0 || y >= rows) return;
-    uint8_t *d = img + (size_t)y * stride + 3 * (size_t)x;
-    d[0] = c0;
-    d[1] = c1;
-    d[2] = c2;
-}
 __global__ __launch_bounds__(256) void draw_lines_parametric_kernel(uint8_t *__restrict__ img, int rows, int cols, size_t stride,
                                                                      const uint32_t *__restrict__ peaks_rc,
                                                                      const int64_t *__restrict__ count_p, unsigned max_peaks,
@@ -227,7 +220,7 @@ __global__ __launch_bounds__(256) void draw_lines_parametric_kernel(uint8_t *__r
     hi = hi > major ? major : hi;
     const long long i = lo + (long long)blockIdx.x * 256 + threadIdx.x;
     if (i > hi) return;
-    const long long m = major == 0 ? 0 : (2 * minor * i + major - 1) / (2 * major);
+    const long long m = line_minor_after(minor, major, i);
     const long long x = steep ? x1 + m : x1 + i, y = steep ? y1 + sy * i : y1 + sy * m;
     put_rgb(img, stride, rows, cols, x, y, c0, c1, c2);
 }

@@ -432,4 +432,163 @@ inline void savePyramid(const std::vector<Mat> &pyramid, const std::string &file
     imwrite(filename, all);
 }
 
+// ---- ps5 driver pieces on the device (include/mi_cv.h, "ps5: driver") ------------------------------------
+// The functions above stay the statement of the contract; the forms below hand the same work to the library and give the
+// same bytes.  (The header's remark "no kernels (a frame has 900 arrows)" holds for large frames only: the lattice
+// strides are max(1, rows / 30) and max(1, cols / 30), so a 59 x 59 frame has 3481 arrows.)
+
+inline void color_bytes(const Scalar &c, unsigned char out[3]) {
+    for (int k = 0; k < 3; k++) out[k] = sat_u8(cv_round(c.v[k]));  // put_pixel's conversion
+}
+
+// drawVelocityVectors through micv_draw_velocity_vectors_host (and micv_gray_or_bgr_to_bgr8_host for a grey image).
+inline void drawVelocityVectorsDevice(Mat &inputImg, const Mat &u, const Mat &v, const Scalar &color) {
+    micv_shim::require(u.rows == v.rows && u.cols == v.cols && u.rows == inputImg.rows && u.cols == inputImg.cols &&
+                           u.type() == micv_shim::F32 && v.type() == micv_shim::F32 && inputImg.depth() == micv_shim::U8 &&
+                           u.step == v.step,
+                       "drawVelocityVectors: image and CV_32FC1 flow fields of equal size expected");
+    if (inputImg.channels() != 3) {
+        Mat rgb(inputImg.rows, inputImg.cols, micv::CV_8UC3);
+        micv_shim::check(micv_gray_or_bgr_to_bgr8_host(micv_shim::context(), inputImg.data, MICV_DEPTH_8U, inputImg.channels(),
+                                                       inputImg.rows, inputImg.cols, inputImg.step, rgb.data, rgb.step));
+        inputImg = rgb;
+    }
+    unsigned char c[3];
+    color_bytes(color, c);
+    micv_shim::check(micv_draw_velocity_vectors_host(micv_shim::context(), inputImg.data, 0, inputImg.step, u.ptr<float>(),
+                                                     v.ptr<float>(), 0, u.step, 1, u.rows, u.cols, c));
+}
+
+// savePyramid through micv_pyramid_montage_host: the four ranges and the montage in two launches.
+inline void savePyramidDevice(const std::vector<Mat> &pyramid, const std::string &filename) {
+    micv_shim::require(pyramid.size() >= 4, "savePyramid: four levels expected");
+    const void *lv[4];
+    int rows[4], cols[4];
+    size_t steps[4];
+    for (int k = 0; k < 4; k++) {
+        micv_shim::require(pyramid[k].type() == pyramid[0].type() && (pyramid[k].type() == micv_shim::F32 || pyramid[k].type() == micv::CV_8UC1),
+                           "savePyramid: four CV_32FC1 or four CV_8UC1 levels expected");
+        lv[k] = pyramid[k].data;
+        rows[k] = pyramid[k].rows;
+        cols[k] = pyramid[k].cols;
+        steps[k] = pyramid[k].step;
+    }
+    Mat all(2 * rows[0], 2 * cols[0], micv::CV_8UC1);
+    micv_shim::check(micv_pyramid_montage_host(micv_shim::context(), lv, rows, cols, steps,
+                                               pyramid[0].type() == micv_shim::F32 ? MICV_DEPTH_32F : MICV_DEPTH_8U, all.data, all.step));
+    imwrite(filename, all);
+}
+
+// warpHelper (Solution.cpp:101-128), the host-loop form: per consecutive pair lk::calcOpticalFlow on level `pyrLevel`,
+// lk::warp, `prev - warped` and cv::normalize on this thread.  Files: <prefix>/<name>-<i>-warped-diff<ext>.  (The
+// reference's denseLKWrapper call inside also draws arrows on the CV_32F level; drawVelocityVectors here takes 8-bit
+// images, so those files are not written.)
+inline void warpHelper(const std::vector<std::vector<Mat>> &pyramids, const int pyrLevel, const size_t winSize,
+                       const std::string &filePrefix, const std::string &filename, const std::string &ext = ".pgm") {
+    for (size_t imIdx = 1; imIdx < pyramids.size(); imIdx++) {
+        const Mat &prev = pyramids[imIdx - 1][pyrLevel], &next = pyramids[imIdx][pyrLevel];
+        Mat du, dv, warped;
+        lk::calcOpticalFlow(prev, next, du, dv, winSize);
+        lk::warp(next, du, dv, warped);
+        Mat diff(prev.rows, prev.cols, micv_shim::F32);
+        for (int y = 0; y < prev.rows; y++)
+            for (int x = 0; x < prev.cols; x++) diff.at<float>(y, x) = prev.at<float>(y, x) - warped.at<float>(y, x);
+        imwrite(filePrefix + "/" + filename + "-" + std::to_string(imIdx) + "-warped-diff" + ext, normalize_minmax_u8(diff));
+    }
+}
+
+// warpHelper on the device: the frames as cv::imread gave them and the pyramid level; grey conversion, the pyramids of
+// all frames, and per pair flow, fused warp-diff and the batched normalisation in ONE library call
+// (micv_ps5_warp_diff_seq_host).  Same files, same bytes.
+inline void warpHelperDevice(const std::vector<Mat> &frames, const int pyrDepth, const int pyrLevel, const size_t winSize,
+                             const std::string &filePrefix, const std::string &filename, const std::string &ext = ".pgm") {
+    micv_shim::require(frames.size() >= 2, "warpHelper: at least two frames expected");
+    const Mat &f0 = frames[0];
+    std::vector<const void *> fp;
+    for (const Mat &f : frames) {
+        micv_shim::require(f.rows == f0.rows && f.cols == f0.cols && f.type() == f0.type() && f.step == f0.step,
+                           "warpHelper: frames of one size, type and row pitch expected");
+        fp.push_back(f.data);
+    }
+    const int lr = f0.rows >> pyrLevel, lc = f0.cols >> pyrLevel;
+    micv_shim::require(lr > 0 && lc > 0, "warpHelper: the level does not fit the frames");
+    const size_t n = (size_t)lr * lc, pairs = frames.size() - 1;
+    std::vector<unsigned char> img(n * pairs);
+    micv_shim::check(micv_ps5_warp_diff_seq_host(micv_shim::context(), fp.data(), (int)frames.size(), f0.rows, f0.cols, f0.step,
+                                                 f0.channels(), micv_shim::depth_code(f0), pyrDepth, pyrLevel, (int)winSize, img.data(),
+                                                 nullptr, nullptr, nullptr));
+    for (size_t p = 0; p < pairs; p++)
+        imwrite(filePrefix + "/" + filename + "-" + std::to_string(p + 1) + "-warped-diff" + ext,
+                Mat(lr, lc, micv::CV_8UC1, img.data() + p * n));
+}
+
+// denseLKWrapper as ONE library call (micv_dense_lk_display_host): both frames go up once; u, v, the arrow image and the
+// two colour maps come back.  8-bit frames of 1 or 3 channels.  Same files, same bytes as denseLKWrapper.
+inline std::pair<Mat, Mat> denseLKWrapperDevice(const Mat &prevImg, const Mat &nextImg, const LKMode mode, const size_t windowSize,
+                                                const std::string &filePrefix, const std::string &outputImg,
+                                                bool saveColorMaps = true, const std::string &ext = ".ppm") {
+    micv_shim::require(prevImg.rows == nextImg.rows && prevImg.cols == nextImg.cols && prevImg.type() == nextImg.type() &&
+                           prevImg.step == nextImg.step,
+                       "denseLKWrapper: frames of one size, type and row pitch expected");
+    const int rows = prevImg.rows, cols = prevImg.cols;
+    Mat uv(2 * rows, cols, micv_shim::F32), arrows(rows, cols, micv::CV_8UC3), jet(2 * rows, cols, micv::CV_8UC3);
+    unsigned char c[3];
+    color_bytes(Scalar(0, 255, 0, 255), c);
+    micv_shim::check(micv_dense_lk_display_host(micv_shim::context(), prevImg.data, nextImg.data, rows, cols, prevImg.step,
+                                                prevImg.channels(), micv_shim::depth_code(prevImg),
+                                                mode == LKMode::NAIVE ? MICV_LK_NAIVE : MICV_LK_PYRAMIDAL, (int)windowSize, 4, c,
+                                                uv.ptr<float>(0), uv.ptr<float>(rows), uv.step, arrows.data, arrows.step,
+                                                saveColorMaps ? jet.ptr<unsigned char>(0) : nullptr,
+                                                saveColorMaps ? jet.ptr<unsigned char>(rows) : nullptr, jet.step));
+    imwrite(filePrefix + "/" + outputImg + ext, arrows);
+    if (saveColorMaps) {
+        imwrite(filePrefix + "/" + outputImg + "-uColorMap" + ext, Mat(rows, cols, micv::CV_8UC3, jet.ptr<unsigned char>(0), jet.step));
+        imwrite(filePrefix + "/" + outputImg + "-vColorMap" + ext, Mat(rows, cols, micv::CV_8UC3, jet.ptr<unsigned char>(rows), jet.step));
+    }
+    return std::make_pair(Mat(rows, cols, micv_shim::F32, uv.ptr<float>(0), uv.step).clone(),
+                          Mat(rows, cols, micv_shim::F32, uv.ptr<float>(rows), uv.step).clone());
+}
+
+// denseLKSequence with the whole tail on the device: the flows of all pairs in one call of the frame-sequence entry, the
+// arrows of all pairs in ONE launch (micv_draw_velocity_vectors_host with batch = pairs) and the colour maps in one batch
+// call.  8-bit frames of 1 or 3 channels.  Same files, same bytes as denseLKSequence.
+inline std::vector<std::pair<Mat, Mat>> denseLKSequenceDevice(const std::vector<Mat> &frames, const size_t windowSize,
+                                                              const std::string &filePrefix, const std::string &outputImg,
+                                                              bool saveColorMaps = true, const std::string &ext = ".ppm") {
+    std::vector<Mat> u, v;
+    lk::calcOpticalFlowPyrSequence(frames, u, v, windowSize);
+    const size_t pairs = u.size();
+    const int rows = u[0].rows, cols = u[0].cols;
+    const size_t n = (size_t)rows * cols;
+    std::vector<float> fields(2 * pairs * n);  // u0 v0 u1 v1 ...
+    std::vector<unsigned char> img(pairs * n * 3), jet(2 * pairs * n * 3);
+    for (size_t p = 0; p < pairs; p++) {
+        for (int k = 0; k < 2; k++) {
+            const Mat &f = k ? v[p] : u[p];
+            for (int y = 0; y < rows; y++) std::memcpy(&fields[(2 * p + k) * n + (size_t)y * cols], f.ptr<float>(y), (size_t)cols * 4);
+        }
+        micv_shim::check(micv_gray_or_bgr_to_bgr8_host(micv_shim::context(), frames[p].data, micv_shim::depth_code(frames[p]),
+                                                       frames[p].channels(), rows, cols, frames[p].step, &img[p * n * 3], (size_t)cols * 3));
+    }
+    unsigned char c[3];
+    color_bytes(Scalar(0, 255, 0, 255), c);
+    micv_shim::check(micv_draw_velocity_vectors_host(micv_shim::context(), img.data(), n * 3, (size_t)cols * 3, fields.data(),
+                                                     fields.data() + n, 2 * n * 4, (size_t)cols * 4, (int)pairs, rows, cols, c));
+    if (saveColorMaps)
+        micv_shim::check(micv_normalize_minmax_batch_host(micv_shim::context(), fields.data(), n * 4, MICV_DEPTH_32F, (int)(2 * pairs), rows,
+                                                          cols, (size_t)cols * 4, nullptr, 0, 0, nullptr, 0, 0, jet.data(), n * 3,
+                                                          (size_t)cols * 3, nullptr));
+    std::vector<std::pair<Mat, Mat>> out;
+    for (size_t p = 0; p < pairs; p++) {
+        const std::string name = outputImg + std::to_string(p);
+        imwrite(filePrefix + "/" + name + ext, Mat(rows, cols, micv::CV_8UC3, &img[p * n * 3]));
+        if (saveColorMaps) {
+            imwrite(filePrefix + "/" + name + "-uColorMap" + ext, Mat(rows, cols, micv::CV_8UC3, &jet[2 * p * n * 3]));
+            imwrite(filePrefix + "/" + name + "-vColorMap" + ext, Mat(rows, cols, micv::CV_8UC3, &jet[(2 * p + 1) * n * 3]));
+        }
+        out.emplace_back(u[p], v[p]);
+    }
+    return out;
+}
+
 }  // namespace micv_viz
