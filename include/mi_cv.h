@@ -1291,6 +1291,92 @@ int micv_dense_lk_display_host(micv_ctx *ctx, const void *prev, const void *next
                                int depth, int mode, int win, int levels, const uint8_t *color, float *u, float *v, size_t ostride,
                                uint8_t *arrows, size_t astride, uint8_t *jet_u, uint8_t *jet_v, size_t jstride);
 
+/* ------------------------------------------------------------------ ps4: driver ------ */
+/* What ProblemSets/ps4_cpp/src/Solution.cpp writes out between harris::, sift::, the matcher and ransac::, on the
+ * device: drawDots (:59-69), cv::hconcat, cv::drawKeypoints with random colours (:147-158), the match lines (:190-207)
+ * and the consensus lines (:240-250).  OpenCV's source is not available to this repository, so its drawing is restated,
+ * PARITY UNPINNED (DESIGN.md sections 2 and 3); the statement of the contract is the host loops of shim/micv_ps4.hpp,
+ * and the `_dev` forms equal them byte for byte.  Every `_dev` entry is asynchronous on `stream`, reads its counts on
+ * the device and never synchronises; every `_host` entry uploads, runs the same kernels and downloads.
+ * Painter's order: every glyph and every line has a colour of its own, and the result is what drawing stroke 0, 1, ..
+ * one after the other would leave: the stroke of the highest index owns a pixel that several strokes cross.
+ * Colours come from cv::RNG (state = (uint32)state * 4164903690 + (state >> 32), a draw is the low word).  One colour
+ * is three draws d0, d1, d2 in that order, reduced modulo m and stored as bytes {d2 % m, d1 % m, d0 % m}: the
+ * reference's toolchain evaluates the arguments of cv::Scalar(..) right to left.  A state or seed of 0 is taken as
+ * 0xffffffff.  At most 2^24 strokes per call. */
+
+/* drawDots: dst (8-bit, 3 channels) = the grey image (MICV_DEPTH_32F converted by saturate_cast<uchar>(cvRound(v)) as
+ * micv_gray_to_rgb8_*, or MICV_DEPTH_8U) replicated to three channels, and (0, 0, 255) where the byte that
+ * micv_normalize_minmax_* stores for `corners` (f32, the sparse map of micv_harris_refine_*) is non-zero.  As the
+ * reference wrote it: a corner weaker than about 1/510 of the strongest is not dotted, a map with a negative entry dots
+ * every pixel except the minimum's, an all-equal map dots nothing, NaN entries are never dotted. */
+int micv_draw_dots_dev(micv_ctx *ctx, const void *gray, int depth, int rows, int cols, size_t gstride, const float *corners,
+                       size_t cstride, uint8_t *dst, size_t dstride, micv_stream stream);
+int micv_draw_dots_host(micv_ctx *ctx, const void *gray, int depth, int rows, int cols, size_t gstride, const float *corners,
+                        size_t cstride, uint8_t *dst, size_t dstride);
+/* cv::hconcat of two 8-bit images of `rows` rows and bpp = 1 or 3 bytes per pixel: dst = [a | b], every side pitched. */
+int micv_hconcat_dev(micv_ctx *ctx, const uint8_t *a, size_t astride, int acols, const uint8_t *b, size_t bstride, int bcols,
+                     int rows, int bpp, uint8_t *dst, size_t dstride, micv_stream stream);
+int micv_hconcat_host(micv_ctx *ctx, const uint8_t *a, size_t astride, int acols, const uint8_t *b, size_t bstride, int bcols,
+                      int rows, int bpp, uint8_t *dst, size_t dstride);
+/* cv::drawKeypoints(src, kp, out, Scalar::all(-1), DRAW_RICH_KEYPOINTS) into the column window [x0, x0 + cols) of a BGR
+ * canvas of canvas_cols columns: the window receives src (8-bit, 1 or 3 channels; NULL: the canvas keeps what it holds)
+ * and then glyph j = 0 .. n-1, n = min(*count, cap) read on the DEVICE (count and kp_xysa as micv_harris_refine_dev and
+ * micv_sift_keypoints_dev leave them).  Glyph j: a thickness-1 circle (the midpoint walk of micv_draw_circles_*) of
+ * centre (cvRound(x), cvRound(y)) and radius cvRound(size / 2), ties to even, and, unless angle == -1, a stroke
+ * (micv_viz::line's walk) from the centre to centre + (cvRound(c * radius), cvRound(s * radius)), (s, c) the fixed
+ * polynomial sine and cosine of the descriptor window at `angle` degrees.  8-connected glyphs are a decision of this
+ * library (OpenCV draws them anti-aliased).  Glyphs are clipped to the window.  A keypoint whose x or y is not finite or
+ * is 1e9 or more in magnitude, or whose size / 2 is not in [0, 32767], draws nothing; an angle that is not finite or is
+ * 1e9 or more in magnitude draws no stroke.  Every keypoint takes its colour (modulo 256) whether it draws or not:
+ * *rng_state (a DEVICE word) advances by exactly 3 n draws, so the next panel continues the generator.
+ * The `_host` form takes n and the state word in host memory. */
+int micv_draw_keypoints_dev(micv_ctx *ctx, const uint8_t *src, int channels, int rows, int cols, size_t sstride, uint8_t *canvas,
+                            int canvas_cols, size_t cstride, int x0, const float *kp_xysa, const int64_t *count, int64_t cap,
+                            uint64_t *rng_state, micv_stream stream);
+int micv_draw_keypoints_host(micv_ctx *ctx, const uint8_t *src, int channels, int rows, int cols, size_t sstride, uint8_t *canvas,
+                             int canvas_cols, size_t cstride, int x0, const float *kp_xysa, int64_t n, uint64_t *rng_state);
+/* The lines of siftHelper and ransacHelper on a BGR canvas (rows x cols, drawn on in place): for match i < n =
+ * min(*count, cap) (matches_qt and the DEVICE count of micv_bf_ratio_filter_dev), from (cvRound(kp_a[q].x),
+ * cvRound(kp_a[q].y)) to (cvRound(kp_b[t].x + x_offset), cvRound(kp_b[t].y)), the sum in float, micv_viz::line's walk,
+ * every pixel bounds-checked.  mask (u8 [cap], or NULL = all): match i is drawn iff mask[i] != 0, so inlier_mask of
+ * micv_ransac_solve*_dev goes straight in.  A match whose q is outside [0, na) or whose t is outside [0, nb) is skipped,
+ * and so are its draws.  The r-th DRAWN line (r = drawn matches before it) takes draws 3r .. 3r+2 (modulo 255:
+ * rng.uniform(0, 255)) of a generator seeded with `seed` per call (the reference: 12345).  A drawn line with an end
+ * point that is not finite or is 1e9 or more in magnitude paints nothing and keeps its draws. */
+int micv_draw_match_lines_dev(micv_ctx *ctx, uint8_t *canvas, int rows, int cols, size_t stride, const float *kp_a, int64_t na,
+                              const float *kp_b, int64_t nb, const int32_t *matches_qt, const int64_t *count, int64_t cap,
+                              const uint8_t *mask, int x_offset, uint64_t seed, micv_stream stream);
+int micv_draw_match_lines_host(micv_ctx *ctx, uint8_t *canvas, int rows, int cols, size_t stride, const float *kp_a, int64_t na,
+                               const float *kp_b, int64_t nb, const int32_t *matches_qt, int64_t n, const uint8_t *mask,
+                               int x_offset, uint64_t seed);
+/* harrisHelper (Solution.cpp:71-132) as one call: micv_harris_corners_dev with its four fields in `fields`
+ * ([4][rows * cols] f32, dense: gx, gy, R, corners), then the three pictures: grad_panel (rows x 2 cols, the normalised
+ * gx beside the normalised gy, :80-86), resp_u8 (the normalised R, :108) and dots (micv_draw_dots of img and corners).
+ * The four ranges come from one min-max launch; the bytes are those of the separate calls. */
+int micv_ps4_harris_display_dev(micv_ctx *ctx, const float *img, int rows, int cols, size_t stride, int sobel_ksize, int win,
+                                double sigma, float alpha, int flags, double threshold, int min_distance, float *fields,
+                                int32_t *locs_yx, int64_t cap, int64_t *count, uint8_t *grad_panel, size_t gstride,
+                                uint8_t *resp_u8, size_t rstride, uint8_t *dots, size_t dstride, micv_stream stream);
+int micv_ps4_harris_display_host(micv_ctx *ctx, const float *img, int rows, int cols, size_t stride, int sobel_ksize, int win,
+                                 double sigma, float alpha, int flags, double threshold, int min_distance, float *fields,
+                                 int32_t *locs_yx, int64_t cap, int64_t *count, uint8_t *grad_panel, size_t gstride,
+                                 uint8_t *resp_u8, size_t rstride, uint8_t *dots, size_t dstride);
+/* The two pictures of siftHelper as one call, asynchronous on one stream: keypoint_panel (optional) = both grey 8-bit
+ * images side by side with their glyphs (A's, then B's continuing *rng_state), match_panel = the same plus the lines
+ * (x_offset = cols_a; the index bounds of the lines are cap_a and cap_b).  With MICV_PS4_NO_GLYPHS no glyph is drawn
+ * and *rng_state stays: match_panel is the grey pair expanded to BGR with the masked lines, ransacHelper's picture. */
+#define MICV_PS4_NO_GLYPHS 1
+int micv_ps4_match_panels_dev(micv_ctx *ctx, const uint8_t *img_a, size_t astride, int cols_a, const uint8_t *img_b, size_t bstride,
+                              int cols_b, int rows, const float *kp_a, const int64_t *count_a, int64_t cap_a, const float *kp_b,
+                              const int64_t *count_b, int64_t cap_b, const int32_t *matches_qt, const int64_t *match_count,
+                              int64_t match_cap, const uint8_t *mask, int flags, uint64_t seed, uint64_t *rng_state,
+                              uint8_t *keypoint_panel, uint8_t *match_panel, size_t pstride, micv_stream stream);
+int micv_ps4_match_panels_host(micv_ctx *ctx, const uint8_t *img_a, size_t astride, int cols_a, const uint8_t *img_b, size_t bstride,
+                               int cols_b, int rows, const float *kp_a, int64_t n_a, const float *kp_b, int64_t n_b,
+                               const int32_t *matches_qt, int64_t n_matches, const uint8_t *mask, int flags, uint64_t seed,
+                               uint64_t *rng_state, uint8_t *keypoint_panel, uint8_t *match_panel, size_t pstride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,7 @@ DEPTH_8U, DEPTH_8S, DEPTH_32F = 0, 1, 5  # mi_cv.h
 DISPARITY_SSD, DISPARITY_NCC = 0, 1  # display (mi_cv.h)
 LK_NAIVE, LK_PYRAMIDAL = 0, 1  # ps5 driver (mi_cv.h)
 WARP_INVERSE_MAP, WARP_NEAREST = 16, 1  # ps4 registration (mi_cv.h)
+PS4_NO_GLYPHS = 1  # ps4 driver (mi_cv.h)
 # micv_ctx_set_option (include/mi_cv.h): none of these changes a result
 (OPT_LK_STREAM_GROUPS, OPT_LK_FORCE_GENERIC, OPT_LK_NARROW_TILES, OPT_SOBEL_GENERIC, OPT_HARRIS_GENERIC,
  OPT_NMS_SCAN, OPT_STEREO_ROWS, OPT_LK_CHAIN, OPT_LK_SHORT_TILES, OPT_LK_STREAM, OPT_LK_TALL_TILES,
@@ -191,6 +192,23 @@ SIGNATURES = {
     "micv_ps5_warp_diff_seq_host": (i32, [vp, C.POINTER(vp), i32, i32, i32, sz, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "micv_dense_lk_display_dev": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp, vp, sz, vp]),
     "micv_dense_lk_display_host": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp, vp, sz]),
+    # ps4 driver
+    "micv_draw_dots_dev": (i32, [vp, vp, i32, i32, i32, sz, vp, sz, vp, sz, vp]),
+    "micv_draw_dots_host": (i32, [vp, vp, i32, i32, i32, sz, vp, sz, vp, sz]),
+    "micv_hconcat_dev": (i32, [vp, vp, sz, i32, vp, sz, i32, i32, i32, vp, sz, vp]),
+    "micv_hconcat_host": (i32, [vp, vp, sz, i32, vp, sz, i32, i32, i32, vp, sz]),
+    "micv_draw_keypoints_dev": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, sz, i32, vp, vp, i64, vp, vp]),
+    "micv_draw_keypoints_host": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, sz, i32, vp, i64, C.POINTER(C.c_uint64)]),
+    "micv_draw_match_lines_dev": (i32, [vp, vp, i32, i32, sz, vp, i64, vp, i64, vp, vp, i64, vp, i32, C.c_uint64, vp]),
+    "micv_draw_match_lines_host": (i32, [vp, vp, i32, i32, sz, vp, i64, vp, i64, vp, i64, vp, i32, C.c_uint64]),
+    "micv_ps4_harris_display_dev": (i32, [vp, vp, i32, i32, sz, i32, i32, f64, f32, i32, f64, i32, vp, vp, i64, vp, vp, sz, vp, sz,
+                                          vp, sz, vp]),
+    "micv_ps4_harris_display_host": (i32, [vp, vp, i32, i32, sz, i32, i32, f64, f32, i32, f64, i32, vp, vp, i64, vp, vp, sz, vp, sz,
+                                           vp, sz]),
+    "micv_ps4_match_panels_dev": (i32, [vp, vp, sz, i32, vp, sz, i32, i32, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, i32,
+                                        C.c_uint64, vp, vp, vp, sz, vp]),
+    "micv_ps4_match_panels_host": (i32, [vp, vp, sz, i32, vp, sz, i32, i32, vp, i64, vp, i64, vp, i64, vp, i32, C.c_uint64,
+                                         C.POINTER(C.c_uint64), vp, vp, sz]),
     # ps4 matching
     "micv_bf_knn2_dev": (i32, [vp, vp, i32, sz, vp, i32, sz, i32, vp, vp, vp]),
     "micv_bf_ratio_filter_dev": (i32, [vp, vp, vp, i32, f64, vp, vp, i64, vp, vp]),

@@ -1631,4 +1631,155 @@ int micv_dense_lk_display_host(micv_ctx *ctx, const void *prev, const void *next
     return MICV_OK;
 }
 
+// ---- ps4 driver (ps4.hip) ----------------------------------------------------------------------
+
+int micv_draw_dots_host(micv_ctx *ctx, const void *gray, int depth, int rows, int cols, size_t gstride, const float *corners,
+                        size_t cstride, uint8_t *dst, size_t dstride) {
+    HOST_PROLOGUE("micv_draw_dots_host");
+    MICV_REQUIRE(gray && corners && dst && rows > 0 && cols > 0, "micv_draw_dots_host: bad argument");
+    MICV_REQUIRE(depth == MICV_DEPTH_8U || depth == MICV_DEPTH_32F, "micv_draw_dots_host: depth %d not supported (8U, 32F)", depth);
+    const size_t e = depth == MICV_DEPTH_32F ? 4 : 1, grb = (size_t)cols * e, crb = (size_t)cols * 4, drb = (size_t)cols * 3;
+    MICV_REQUIRE(stride_ok(gstride, cols, e) && stride_ok(cstride, cols, 4) && dstride >= drb, "micv_draw_dots_host: bad stride");
+    DevBuf dg(grb * rows), dc(crb * rows), dd(drb * rows);
+    MICV_ALLOC_OK(dg); MICV_ALLOC_OK(dc); MICV_ALLOC_OK(dd);
+    MICV_TRY(up2d(dg.p, gray, gstride, grb, rows, s));
+    MICV_TRY(up2d(dc.p, corners, cstride, crb, rows, s));
+    MICV_TRY(micv_draw_dots_dev(ctx, dg.p, depth, rows, cols, grb, dc.as<float>(), crb, dd.as<uint8_t>(), drb, s));
+    MICV_TRY(down2d(dst, dstride, dd.p, drb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_hconcat_host(micv_ctx *ctx, const uint8_t *a, size_t astride, int acols, const uint8_t *b, size_t bstride, int bcols,
+                      int rows, int bpp, uint8_t *dst, size_t dstride) {
+    HOST_PROLOGUE("micv_hconcat_host");
+    MICV_REQUIRE(a && b && dst && rows > 0 && acols > 0 && bcols > 0 && (bpp == 1 || bpp == 3), "micv_hconcat_host: bad argument");
+    const size_t arb = (size_t)acols * bpp, brb = (size_t)bcols * bpp;
+    MICV_REQUIRE(astride >= arb && bstride >= brb && dstride >= arb + brb, "micv_hconcat_host: a stride is smaller than its row");
+    DevBuf da(arb * rows), db(brb * rows), dd((arb + brb) * rows);
+    MICV_ALLOC_OK(da); MICV_ALLOC_OK(db); MICV_ALLOC_OK(dd);
+    MICV_TRY(up2d(da.p, a, astride, arb, rows, s));
+    MICV_TRY(up2d(db.p, b, bstride, brb, rows, s));
+    MICV_TRY(micv_hconcat_dev(ctx, da.as<uint8_t>(), arb, acols, db.as<uint8_t>(), brb, bcols, rows, bpp, dd.as<uint8_t>(), arb + brb, s));
+    MICV_TRY(down2d(dst, dstride, dd.p, arb + brb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_draw_keypoints_host(micv_ctx *ctx, const uint8_t *src, int channels, int rows, int cols, size_t sstride, uint8_t *canvas,
+                             int canvas_cols, size_t cstride, int x0, const float *kp_xysa, int64_t n, uint64_t *rng_state) {
+    HOST_PROLOGUE("micv_draw_keypoints_host");
+    MICV_REQUIRE(canvas && rng_state && rows > 0 && cols > 0 && n >= 0 && (n == 0 || kp_xysa), "micv_draw_keypoints_host: bad argument");
+    MICV_REQUIRE(!src || channels == 1 || channels == 3, "micv_draw_keypoints_host: %d channels not supported (1 or 3)", channels);
+    MICV_REQUIRE(x0 >= 0 && (int64_t)x0 + cols <= canvas_cols && cstride >= (size_t)canvas_cols * 3 &&
+                     (!src || sstride >= (size_t)cols * channels),
+                 "micv_draw_keypoints_host: the window does not lie in the canvas, or bad stride");
+    // the window alone travels: it is a canvas of its own on the device
+    const size_t srb = src ? (size_t)cols * channels : 16, prb = (size_t)cols * 3;
+    DevBuf ds(srb * rows), dp(prb * rows), dk(n ? (size_t)n * 16 : 16), dw(16);
+    MICV_ALLOC_OK(ds); MICV_ALLOC_OK(dp); MICV_ALLOC_OK(dk); MICV_ALLOC_OK(dw);
+    uint8_t *window = canvas + 3 * (size_t)x0;
+    if (src)
+        MICV_TRY(up2d(ds.p, src, sstride, srb, rows, s));
+    else
+        MICV_TRY(up2d(dp.p, window, cstride, prb, rows, s));
+    if (n) MICV_HIP(hipMemcpyAsync(dk.p, kp_xysa, (size_t)n * 16, hipMemcpyHostToDevice, s));
+    const int64_t words[2] = {n, (int64_t)*rng_state};
+    MICV_HIP(hipMemcpyAsync(dw.p, words, 16, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_draw_keypoints_dev(ctx, src ? ds.as<uint8_t>() : nullptr, channels, rows, cols, srb, dp.as<uint8_t>(), cols, prb, 0,
+                                     dk.as<float>(), dw.as<int64_t>(), n, reinterpret_cast<uint64_t *>(dw.as<int64_t>() + 1), s));
+    MICV_TRY(down2d(window, cstride, dp.p, prb, rows, s));
+    MICV_HIP(hipMemcpyAsync(rng_state, dw.as<int64_t>() + 1, 8, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_draw_match_lines_host(micv_ctx *ctx, uint8_t *canvas, int rows, int cols, size_t stride, const float *kp_a, int64_t na,
+                               const float *kp_b, int64_t nb, const int32_t *matches_qt, int64_t n, const uint8_t *mask,
+                               int x_offset, uint64_t seed) {
+    HOST_PROLOGUE("micv_draw_match_lines_host");
+    MICV_REQUIRE(canvas && rows > 0 && cols > 0 && stride >= (size_t)cols * 3 && na >= 0 && nb >= 0 && n >= 0,
+                 "micv_draw_match_lines_host: bad argument");
+    if (n == 0 || na == 0 || nb == 0) return MICV_OK;
+    MICV_REQUIRE(kp_a && kp_b && matches_qt, "micv_draw_match_lines_host: null argument");
+    const size_t rb = (size_t)cols * 3;
+    DevBuf dc(rb * rows), da((size_t)na * 16), db((size_t)nb * 16), dm((size_t)n * 8), dk(mask ? (size_t)n : 16), dw(8);
+    MICV_ALLOC_OK(dc); MICV_ALLOC_OK(da); MICV_ALLOC_OK(db); MICV_ALLOC_OK(dm); MICV_ALLOC_OK(dk); MICV_ALLOC_OK(dw);
+    MICV_TRY(up2d(dc.p, canvas, stride, rb, rows, s));
+    MICV_HIP(hipMemcpyAsync(da.p, kp_a, (size_t)na * 16, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(db.p, kp_b, (size_t)nb * 16, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(dm.p, matches_qt, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    if (mask) MICV_HIP(hipMemcpyAsync(dk.p, mask, (size_t)n, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(dw.p, &n, 8, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_draw_match_lines_dev(ctx, dc.as<uint8_t>(), rows, cols, rb, da.as<float>(), na, db.as<float>(), nb, dm.as<int32_t>(),
+                                       dw.as<int64_t>(), n, mask ? dk.as<uint8_t>() : nullptr, x_offset, seed, s));
+    MICV_TRY(down2d(canvas, stride, dc.p, rb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_ps4_harris_display_host(micv_ctx *ctx, const float *img, int rows, int cols, size_t stride, int sobel_ksize, int win,
+                                 double sigma, float alpha, int flags, double threshold, int min_distance, float *fields,
+                                 int32_t *locs_yx, int64_t cap, int64_t *count, uint8_t *grad_panel, size_t gstride,
+                                 uint8_t *resp_u8, size_t rstride, uint8_t *dots, size_t dstride) {
+    HOST_PROLOGUE("micv_ps4_harris_display_host");
+    MICV_REQUIRE(img && fields && count && grad_panel && resp_u8 && dots && rows > 0 && cols > 0 && cap >= 0 && (cap == 0 || locs_yx),
+                 "micv_ps4_harris_display_host: bad argument");
+    const size_t n = (size_t)rows * cols, rb = (size_t)cols * 4;
+    MICV_REQUIRE(stride_ok(stride, cols, 4) && gstride >= (size_t)2 * cols && rstride >= (size_t)cols && dstride >= (size_t)cols * 3,
+                 "micv_ps4_harris_display_host: bad stride");
+    DevBuf di(n * 4), df(n * 16), dl(cap ? (size_t)cap * 8 : 16), dn(8), dg(2 * n), dr(n), dd(3 * n);
+    MICV_ALLOC_OK(di); MICV_ALLOC_OK(df); MICV_ALLOC_OK(dl); MICV_ALLOC_OK(dn); MICV_ALLOC_OK(dg); MICV_ALLOC_OK(dr); MICV_ALLOC_OK(dd);
+    MICV_TRY(up2d(di.p, img, stride, rb, rows, s));
+    MICV_TRY(micv_ps4_harris_display_dev(ctx, di.as<float>(), rows, cols, rb, sobel_ksize, win, sigma, alpha, flags, threshold,
+                                         min_distance, df.as<float>(), dl.as<int32_t>(), cap, dn.as<int64_t>(), dg.as<uint8_t>(),
+                                         (size_t)2 * cols, dr.as<uint8_t>(), (size_t)cols, dd.as<uint8_t>(), (size_t)3 * cols, s));
+    MICV_HIP(hipMemcpyAsync(fields, df.p, n * 16, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipMemcpyAsync(count, dn.p, 8, hipMemcpyDeviceToHost, s));
+    MICV_TRY(down2d(grad_panel, gstride, dg.p, (size_t)2 * cols, rows, s));
+    MICV_TRY(down2d(resp_u8, rstride, dr.p, (size_t)cols, rows, s));
+    MICV_TRY(down2d(dots, dstride, dd.p, (size_t)3 * cols, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    if (cap) {
+        const int64_t got = *count < cap ? *count : cap;
+        if (got > 0) MICV_HIP(hipMemcpy(locs_yx, dl.p, (size_t)got * 8, hipMemcpyDeviceToHost));
+    }
+    return MICV_OK;
+}
+
+int micv_ps4_match_panels_host(micv_ctx *ctx, const uint8_t *img_a, size_t astride, int cols_a, const uint8_t *img_b, size_t bstride,
+                               int cols_b, int rows, const float *kp_a, int64_t n_a, const float *kp_b, int64_t n_b,
+                               const int32_t *matches_qt, int64_t n_matches, const uint8_t *mask, int flags, uint64_t seed,
+                               uint64_t *rng_state, uint8_t *keypoint_panel, uint8_t *match_panel, size_t pstride) {
+    HOST_PROLOGUE("micv_ps4_match_panels_host");
+    MICV_REQUIRE(img_a && img_b && match_panel && rng_state && rows > 0 && cols_a > 0 && cols_b > 0 && n_a >= 0 && n_b >= 0 &&
+                     n_matches >= 0 && (n_a == 0 || kp_a) && (n_b == 0 || kp_b) && (n_matches == 0 || matches_qt),
+                 "micv_ps4_match_panels_host: bad argument");
+    const size_t prb = ((size_t)cols_a + cols_b) * 3;
+    MICV_REQUIRE(astride >= (size_t)cols_a && bstride >= (size_t)cols_b && pstride >= prb, "micv_ps4_match_panels_host: bad stride");
+    DevBuf da((size_t)cols_a * rows), db((size_t)cols_b * rows), dka(n_a ? (size_t)n_a * 16 : 16), dkb(n_b ? (size_t)n_b * 16 : 16),
+        dm(n_matches ? (size_t)n_matches * 8 : 16), dk(mask && n_matches ? (size_t)n_matches : 16), dw(32), dp1(keypoint_panel ? prb * rows : 16),
+        dp2(prb * rows);
+    MICV_ALLOC_OK(da); MICV_ALLOC_OK(db); MICV_ALLOC_OK(dka); MICV_ALLOC_OK(dkb); MICV_ALLOC_OK(dm); MICV_ALLOC_OK(dk); MICV_ALLOC_OK(dw);
+    MICV_ALLOC_OK(dp1); MICV_ALLOC_OK(dp2);
+    MICV_TRY(up2d(da.p, img_a, astride, (size_t)cols_a, rows, s));
+    MICV_TRY(up2d(db.p, img_b, bstride, (size_t)cols_b, rows, s));
+    if (n_a) MICV_HIP(hipMemcpyAsync(dka.p, kp_a, (size_t)n_a * 16, hipMemcpyHostToDevice, s));
+    if (n_b) MICV_HIP(hipMemcpyAsync(dkb.p, kp_b, (size_t)n_b * 16, hipMemcpyHostToDevice, s));
+    if (n_matches) MICV_HIP(hipMemcpyAsync(dm.p, matches_qt, (size_t)n_matches * 8, hipMemcpyHostToDevice, s));
+    if (mask && n_matches) MICV_HIP(hipMemcpyAsync(dk.p, mask, (size_t)n_matches, hipMemcpyHostToDevice, s));
+    const int64_t words[4] = {n_a, n_b, n_matches, (int64_t)*rng_state};
+    MICV_HIP(hipMemcpyAsync(dw.p, words, 32, hipMemcpyHostToDevice, s));
+    int64_t *w = dw.as<int64_t>();
+    MICV_TRY(micv_ps4_match_panels_dev(ctx, da.as<uint8_t>(), (size_t)cols_a, cols_a, db.as<uint8_t>(), (size_t)cols_b, cols_b, rows,
+                                       dka.as<float>(), w, n_a, dkb.as<float>(), w + 1, n_b, dm.as<int32_t>(), w + 2, n_matches,
+                                       mask ? dk.as<uint8_t>() : nullptr, flags, seed, reinterpret_cast<uint64_t *>(w + 3),
+                                       keypoint_panel ? dp1.as<uint8_t>() : nullptr, dp2.as<uint8_t>(), prb, s));
+    if (keypoint_panel) MICV_TRY(down2d(keypoint_panel, pstride, dp1.p, prb, rows, s));
+    MICV_TRY(down2d(match_panel, pstride, dp2.p, prb, rows, s));
+    MICV_HIP(hipMemcpyAsync(rng_state, w + 3, 8, hipMemcpyDeviceToHost, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
 }  // extern "C"

@@ -13,14 +13,6 @@
 
 namespace micv {
 
-// saturate_cast<uchar>(cvRound(v)): cvRound is x86's cvtss2si -- half to even, and INT_MIN for NaN, +-inf and every
-// value outside int, which then saturates to 0.
-__device__ __forceinline__ uint8_t f32_to_u8(float v) {
-    if (!(v >= -2147483648.f && v < 2147483648.f)) return 0;
-    const int r = (int)rintf(v);
-    return (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
-}
-
 template <typename T>
 __device__ __forceinline__ T *row_ptr(T *base, size_t stride_bytes, int y) {
     return reinterpret_cast<T *>(reinterpret_cast<char *>(const_cast<typename std::remove_const<T>::type *>(base)) +
