@@ -919,8 +919,9 @@ int micv_disparity_pair_display_host(micv_ctx *ctx, const float *left, const flo
  *     cvRound; MICV_PF_MSE blends into the model patch; MICV_PF_HIST always blends from the ORIGINAL model
  *     patch (the reference never updates _modelPatch there) and the blend's normalized histogram becomes
  *     the model histogram.
- * The model is copied at create (the reference's driver keeps a view into frame 0 and paints particles
- * and the bounding box into it; that is not reproduced). */
+ * The model is copied at create: the reference's driver keeps a view into frame 0, into which it then paints particles
+ * and the bounding box.  The painting is reproduced ("ps6: driver" below); the view is not: the model stays a copy,
+ * so the tracker never sees the paint. */
 #define MICV_PF_MSE  0 /* ParticleFilter::SimilarityMode::MEAN_SQ_ERR */
 #define MICV_PF_HIST 1 /* ParticleFilter::SimilarityMode::MEAN_SHIFT_LT */
 #define MICV_PF_MSE_SIGNED 1u /* flag: the intended (m - c)^2 instead of the saturating u8 arithmetic */
@@ -1376,6 +1377,65 @@ int micv_ps4_match_panels_host(micv_ctx *ctx, const uint8_t *img_a, size_t astri
                                int cols_b, int rows, const float *kp_a, int64_t n_a, const float *kp_b, int64_t n_b,
                                const int32_t *matches_qt, int64_t n_matches, const uint8_t *mask, int flags, uint64_t seed,
                                uint64_t *rng_state, uint8_t *keypoint_panel, uint8_t *match_panel, size_t pstride);
+
+/* ------------------------------------------------------------------ ps6: driver ------ */
+/* What pfDriver (ProblemSets/ps6_cpp/src/Solution.cpp:16-107) does around ParticleFilter::tick, on the device: the dot
+ * per particle of ParticleFilter::drawParticles, cv::rectangle around the estimate, and the loop itself with the frames
+ * the driver keeps coming back annotated.  OpenCV's source is not available to this repository, so its drawing is
+ * restated, PARITY UNPINNED ("ps6 driver"); the statement of the contract is the two host loops of
+ * the shim, ParticleFilter::drawParticles (shim/micv_shim.hpp) and micv_viz::rectangle (shim/micv_viz.hpp), and the
+ * device forms equal them byte for byte.  Every `_dev` entry is asynchronous on `stream`, reads particles and the
+ * estimate on the device and never synchronises; MICV_EINVAL is returned before anything is enqueued.
+ * Images: 8-bit, 1, 3 or 4 interleaved channels, rows and cols in 1 .. 32767, `stride` bytes per row (>= cols *
+ * channels, < 2^32); only the first min(channels, 4) bytes of a painted pixel are written, padding never.
+ * Colours: four doubles; byte k of a painted pixel is saturate(nearbyint(color[k])) (NaN gives 0).
+ * Dots (cv::circle(img, p, 1, color, -1) restated): a particle is skipped unless -2 < p.x < cols + 2 and
+ *   -2 < p.y < rows + 2 in float (NaN is skipped); the centre is (nearbyint(p.x), nearbyint(p.y)), halves to even; the
+ *   dot is the centre and its four neighbours, each clipped to the image.
+ * Rectangle (cv::rectangle(img, Rect(x, y, w, h), color), thickness 1): nothing when w <= 0 or h <= 0, otherwise the
+ *   one-pixel ring of [x, x + w - 1] x [y, y + h - 1] (64-bit arithmetic, x may be INT_MIN) intersected with the image.
+ * The driver's box around the estimate c (:76-78), bbox_w and bbox_h floats: x = cvRound(c.x - bbox_w / 2),
+ *   y = cvRound(c.y - bbox_h / 2), w = cvRound(bbox_w), h = cvRound(bbox_h), the subtraction and the halving in float;
+ *   cvRound rounds halves to even and gives INT_MIN for NaN, +-inf and every value outside int.
+ * Order: dots first, box second; the box wins wherever they overlap.  All in one launch. */
+/* xy: n x {x, y} f32 (device for _dev), 0 <= n; n = 0 is a no-op. */
+int micv_draw_particles_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *xy, int n,
+                            const double *color, micv_stream stream);
+int micv_draw_particles_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *xy, int n,
+                             const double *color);
+int micv_draw_rectangle_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, int x, int y, int w, int h,
+                            const double *color, micv_stream stream);
+int micv_draw_rectangle_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, int x, int y, int w, int h,
+                             const double *color);
+/* The driver's overlay of a caller's particle list: the dots, then the box around centre[0..1] (device memory for _dev:
+ * the estimate where a chain left it). */
+int micv_ps6_overlay_list_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *xy, int n,
+                              const double *dot_color, const float *centre, float bbox_w, float bbox_h, const double *box_color,
+                              micv_stream stream);
+int micv_ps6_overlay_list_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *xy, int n,
+                               const double *dot_color, const float *centre, float bbox_w, float bbox_h, const double *box_color);
+/* The same from the filter's own device state, in place in `frame` (device, the filter's rows x cols x channels): its
+ * current particles and the box around its current mean.  Ordered behind the ticks enqueued on `stream`. */
+int micv_ps6_overlay_dev(micv_pf *pf, uint8_t *frame, size_t stride, const double *dot_color, float bbox_w, float bbox_h,
+                         const double *box_color, micv_stream stream);
+/* One pass of pfDriver's loop body: micv_pf_tick_dev on `frame`, then the overlay into `out`.  out may be the frame
+ * itself (then ostride == stride); a separate out receives a copy of the frame first and the frame stays as it is.  The
+ * overlay is ordered after the model update, so the tracker never sees the paint.  _host: upload, the same, download of
+ * out and the state, sync (null stream, as micv_pf_tick_host). */
+int micv_ps6_tick_display_dev(micv_pf *pf, const uint8_t *frame, size_t stride, uint8_t *out, size_t ostride, const double *dot_color,
+                              float bbox_w, float bbox_h, const double *box_color, micv_stream stream, micv_pf_state *state_dev);
+int micv_ps6_tick_display_host(micv_pf *pf, const uint8_t *frame, size_t stride, uint8_t *out, size_t ostride, const double *dot_color,
+                               float bbox_w, float bbox_h, const double *box_color, micv_pf_state *state);
+/* pfDriver as one call over host frames, on the pattern of micv_pf_track_seq_host: two frame buffers, the upload of
+ * frame t + 1 beside tick t, the overlay painted in place in the device buffer, and a download of only the frames that
+ * are kept: out_frames[k] (rows x cols x channels u8, ostride bytes per row) receives frame save[k] (0-based, the
+ * driver's saveFrames; an index may repeat), or with all_frames != 0 frame k for every k < nframes (what the driver
+ * hands to the video writer; save is ignored).  The next upload into a buffer waits for that buffer's download.  states:
+ * nframes entries, bit-identical to micv_pf_track_seq_host.  MICV_EINVAL for a save index outside 0 .. nframes - 1.
+ * Two streams of its own, like micv_pf_track_seq_host.  Blocking. */
+int micv_ps6_track_display_seq_host(micv_pf *pf, const uint8_t *const *frames, int nframes, size_t stride, const double *dot_color,
+                                    float bbox_w, float bbox_h, const double *box_color, const int *save, int nsave, int all_frames,
+                                    uint8_t *const *out_frames, size_t ostride, micv_pf_state *states);
 
 #ifdef __cplusplus
 }

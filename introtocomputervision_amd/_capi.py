@@ -260,6 +260,17 @@ SIGNATURES = {
     "micv_pf_weights_host": (i32, [vp, vp]),
     "micv_pf_model_host": (i32, [vp, vp, vp]),
     "micv_pf_track_seq_host": (i32, [vp, vp, i32, sz, vp, vp]),
+    # ps6 driver
+    "micv_draw_particles_dev": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, vp, vp]),
+    "micv_draw_particles_host": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, vp]),
+    "micv_draw_rectangle_dev": (i32, [vp, vp, i32, i32, i32, sz, i32, i32, i32, i32, vp, vp]),
+    "micv_draw_rectangle_host": (i32, [vp, vp, i32, i32, i32, sz, i32, i32, i32, i32, vp]),
+    "micv_ps6_overlay_list_dev": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, vp, vp, f32, f32, vp, vp]),
+    "micv_ps6_overlay_list_host": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, vp, vp, f32, f32, vp]),
+    "micv_ps6_overlay_dev": (i32, [vp, vp, sz, vp, f32, f32, vp, vp]),
+    "micv_ps6_tick_display_dev": (i32, [vp, vp, sz, vp, sz, vp, f32, f32, vp, vp, vp]),
+    "micv_ps6_tick_display_host": (i32, [vp, vp, sz, vp, sz, vp, f32, f32, vp, vp]),
+    "micv_ps6_track_display_seq_host": (i32, [vp, vp, i32, sz, vp, f32, f32, vp, vp, i32, i32, vp, sz, vp]),
     # ps7
     "micv_mhi_frame_difference_dev": (i32, [vp, vp, vp, i32, i32, sz, f64, i32, i32, f64, vp, sz, vp]),
     "micv_mhi_energy_dev": (i32, [vp, vp, i32, i32, sz, vp, sz, vp]),

@@ -1782,4 +1782,62 @@ int micv_ps4_match_panels_host(micv_ctx *ctx, const uint8_t *img_a, size_t astri
     return MICV_OK;
 }
 
+// ---- ps6 driver (ps6.hip) ----------------------------------------------------------------------
+// The image goes up with its pixels only; the padding of the caller's rows is never read or written.
+
+int micv_draw_particles_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *xy, int n,
+                             const double *color) {
+    HOST_PROLOGUE("micv_draw_particles_host");
+    MICV_REQUIRE(img && color && rows > 0 && cols > 0 && n >= 0 && (n == 0 || xy), "micv_draw_particles_host: bad argument");
+    MICV_REQUIRE(channels == 1 || channels == 3 || channels == 4, "micv_draw_particles_host: %d channels not supported (1, 3, 4)", channels);
+    const size_t rb = (size_t)cols * channels;
+    MICV_REQUIRE(stride >= rb, "micv_draw_particles_host: stride %zu < %zu", stride, rb);
+    if (n == 0) return MICV_OK;
+    DevBuf di(rb * rows), dp((size_t)n * 8);
+    MICV_ALLOC_OK(di); MICV_ALLOC_OK(dp);
+    MICV_TRY(up2d(di.p, img, stride, rb, rows, s));
+    MICV_HIP(hipMemcpyAsync(dp.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_draw_particles_dev(ctx, di.as<uint8_t>(), rows, cols, channels, rb, dp.as<float>(), n, color, s));
+    MICV_TRY(down2d(img, stride, di.p, rb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_draw_rectangle_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, int x, int y, int w, int h,
+                             const double *color) {
+    HOST_PROLOGUE("micv_draw_rectangle_host");
+    MICV_REQUIRE(img && color && rows > 0 && cols > 0, "micv_draw_rectangle_host: bad argument");
+    MICV_REQUIRE(channels == 1 || channels == 3 || channels == 4, "micv_draw_rectangle_host: %d channels not supported (1, 3, 4)", channels);
+    const size_t rb = (size_t)cols * channels;
+    MICV_REQUIRE(stride >= rb, "micv_draw_rectangle_host: stride %zu < %zu", stride, rb);
+    DevBuf di(rb * rows);
+    MICV_ALLOC_OK(di);
+    MICV_TRY(up2d(di.p, img, stride, rb, rows, s));
+    MICV_TRY(micv_draw_rectangle_dev(ctx, di.as<uint8_t>(), rows, cols, channels, rb, x, y, w, h, color, s));
+    MICV_TRY(down2d(img, stride, di.p, rb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
+int micv_ps6_overlay_list_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *xy, int n,
+                               const double *dot_color, const float *centre, float bbox_w, float bbox_h, const double *box_color) {
+    HOST_PROLOGUE("micv_ps6_overlay_list_host");
+    MICV_REQUIRE(img && dot_color && centre && box_color && rows > 0 && cols > 0 && n >= 0 && (n == 0 || xy),
+                 "micv_ps6_overlay_list_host: bad argument");
+    MICV_REQUIRE(channels == 1 || channels == 3 || channels == 4, "micv_ps6_overlay_list_host: %d channels not supported (1, 3, 4)",
+                 channels);
+    const size_t rb = (size_t)cols * channels;
+    MICV_REQUIRE(stride >= rb, "micv_ps6_overlay_list_host: stride %zu < %zu", stride, rb);
+    DevBuf di(rb * rows), dp(n ? (size_t)n * 8 : 16), dc(16);
+    MICV_ALLOC_OK(di); MICV_ALLOC_OK(dp); MICV_ALLOC_OK(dc);
+    MICV_TRY(up2d(di.p, img, stride, rb, rows, s));
+    if (n) MICV_HIP(hipMemcpyAsync(dp.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    MICV_HIP(hipMemcpyAsync(dc.p, centre, 8, hipMemcpyHostToDevice, s));
+    MICV_TRY(micv_ps6_overlay_list_dev(ctx, di.as<uint8_t>(), rows, cols, channels, rb, dp.as<float>(), n, dot_color, dc.as<float>(), bbox_w,
+                                       bbox_h, box_color, s));
+    MICV_TRY(down2d(img, stride, di.p, rb, rows, s));
+    MICV_HIP(hipStreamSynchronize(s));
+    return MICV_OK;
+}
+
 }  // extern "C"

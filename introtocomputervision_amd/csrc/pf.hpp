@@ -1,0 +1,37 @@
+// pf.hpp -- the particle filter's handle (pf.hip) for the files that work on its device state (ps6.hip: the driver's
+// overlay reads the particles and the estimate where the tick left them).
+#pragma once
+#include "common.hpp"
+
+struct micv_pf {
+    int device = 0;
+    int mrows = 0, mcols = 0, ch = 0, rows = 0, cols = 0, n = 0, mode = 0;
+    uint32_t flags = 0;
+    double mse_sigma = 0;
+    float fa = 0, fb = 0;  // (float)alpha, (float)(1 - alpha)
+    float2 *parts = nullptr, *moved = nullptr;  // current particles; displaced particles of the running tick
+    double2 *disp = nullptr;                    // displacement table
+    float *uni = nullptr;                       // resampling uniforms
+    double *sim = nullptr;
+    float *weights = nullptr;
+    uint8_t *model = nullptr, *model0 = nullptr;  // current model patch / last blend; the original patch
+    float *hist = nullptr;                        // model histogram [ch][32]
+    micv_pf_state *state = nullptr;
+    uint8_t *frame_buf[2] = {nullptr, nullptr};   // host-frame staging of tick_host / track_seq_host
+    ~micv_pf() {
+        (void)hipSetDevice(device);
+        for (void *p : {(void *)parts, (void *)moved, (void *)disp, (void *)uni, (void *)sim, (void *)weights,
+                        (void *)model, (void *)model0, (void *)hist, (void *)state, (void *)frame_buf[0],
+                        (void *)frame_buf[1]})
+            if (p) (void)hipFree(p);
+    }
+    size_t patch_bytes() const { return (size_t)mrows * mcols * ch; }
+    size_t frame_bytes() const { return (size_t)rows * cols * ch; }
+};
+
+namespace micv {
+// The three launches of one tick on `s` (pf.hip); the state also goes to state_out (device, may be NULL).
+int pf_enqueue_tick(micv_pf *pf, const uint8_t *frame, size_t stride, hipStream_t s, micv_pf_state *state_out);
+// Allocates pf->frame_buf[0..1] (dense rows x cols x ch) on first use.
+int pf_frame_buffers(micv_pf *pf);
+}  // namespace micv

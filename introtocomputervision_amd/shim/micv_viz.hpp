@@ -219,6 +219,37 @@ inline void line(Mat &img, Point p1, Point p2, const Scalar &color) {
     }
 }
 
+struct Rect {
+    int x = 0, y = 0, width = 0, height = 0;
+    Rect() = default;
+    Rect(int x_, int y_, int w, int h) : x(x_), y(y_), width(w), height(h) {}
+};
+
+// cv::rectangle(img, rec, color) at its defaults (thickness 1, LINE_8, shift 0): nothing for an empty rectangle, otherwise
+// the four strokes tl -> (br.x - 1, tl.y) -> br - (1, 1) -> (tl.x, br.y - 1) -> tl, the one-pixel ring of
+// [x, x + w - 1] x [y, y + h - 1] inside the image.  The corners are taken in 64 bits (x may be INT_MIN, x + w may pass
+// INT_MAX); every stroke is parallel to an axis, so it is cut to the image before the walk, which then visits the same
+// in-image pixels in ints.  The statement of the contract for micv_draw_rectangle_* (parity with OpenCV's rasteriser unpinned).
+inline void rectangle(Mat &img, const Rect &rec, const Scalar &color) {
+    if (rec.width <= 0 || rec.height <= 0) return;
+    const long long x0 = rec.x, y0 = rec.y, x1 = x0 + rec.width - 1, y1 = y0 + rec.height - 1;
+    auto stroke = [&](long long ax, long long ay, long long bx, long long by) {
+        if (ay == by) {  // along x
+            if (ay < 0 || ay >= img.rows) return;
+            const long long lo = std::max<long long>(std::min(ax, bx), 0), hi = std::min<long long>(std::max(ax, bx), img.cols - 1);
+            if (lo <= hi) line(img, Point{(int)lo, (int)ay}, Point{(int)hi, (int)ay}, color);
+        } else {  // along y
+            if (ax < 0 || ax >= img.cols) return;
+            const long long lo = std::max<long long>(std::min(ay, by), 0), hi = std::min<long long>(std::max(ay, by), img.rows - 1);
+            if (lo <= hi) line(img, Point{(int)ax, (int)lo}, Point{(int)ax, (int)hi}, color);
+        }
+    };
+    stroke(x0, y0, x1, y0);
+    stroke(x1, y0, x1, y1);
+    stroke(x1, y1, x0, y1);
+    stroke(x0, y1, x0, y0);
+}
+
 // cv::arrowedLine(img, pt1, pt2, color) with the defaults thickness 1, LINE_8, shift 0, tipLength 0.1.
 inline void arrowed_line(Mat &img, float x1, float y1, float x2, float y2, const Scalar &color) {
     const Point p1{cv_round(x1), cv_round(y1)}, p2{cv_round(x2), cv_round(y2)};  // Point2f -> Point: saturate_cast<int>
