@@ -1,12 +1,12 @@
 """Exact numpy restatement of ps7's second half as include/mi_cv.h states it: moments::centralMoment (Moments.cpp),
 cv::ml::KNearest + matching::{naiveConfusionMatrix, confusionMatrix} (Matching.cpp) and mhiHelper's loop
-(Solution.cpp:16-101, through the CPU oracle's MHI functions).  Every f32 step is a numpy float32 operation (IEEE,
+(Solution.cpp:16-101, through tests/_mhi_ref.py, the oracle-free restatement of MotionHistory.cpp / .cu).  Every f32 step is a numpy float32 operation (IEEE,
 no FMA); every sum is math.fsum (the exact sum rounded once to double) then float32."""
 import math
 
 import numpy as np
 
-import _oracle as orc
+import _mhi_ref as mhi_ref
 
 QNAN = np.uint32(0x7FC00000).view(np.float32)
 FLT_MAX_BITS = 0x7F7FFFFF
@@ -261,14 +261,12 @@ def group_confusion(features, labels, groups, num_groups, num_labels=3, k=3, f64
 
 def history_seq(frames, thresh, blur, sigma, tau, save):
     """mhiHelper: the history after update j for every j in save."""
-    hist = np.zeros(frames.shape[1:], np.uint8)
-    want = {}
-    for f in range(1, max(save) + 1):
-        diff = orc.mhi_frame_difference(frames[f - 1], frames[f], thresh, blur, sigma)
-        hist = orc.mhi_update(hist, diff, tau)
-        if f in save:
-            want[f] = hist.copy()
-    return np.stack([want[j] for j in save])
+    return mhi_ref.history_seq(frames, thresh, blur, sigma, tau, list(save))
+
+
+def mhi_energy(mhi):
+    """mhi::energyFromHistory."""
+    return mhi_ref.energy(mhi)
 
 
 # --------------------------------------------------------------------------------------------- synthetic ps7 ----

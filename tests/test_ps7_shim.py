@@ -61,7 +61,7 @@ def test_problem2_through_the_shim(tmp_path):
     mu, eta = [], []
     for i, m in enumerate(mhis):
         a, b, _ = ref.central_moments(m, ref.PS7_ORDERS, norm_inf=True)
-        c, d, _ = ref.central_moments(ref.orc.mhi_energy(m), ref.PS7_ORDERS)
+        c, d, _ = ref.central_moments(ref.mhi_energy(m), ref.PS7_ORDERS)
         got = np.array([float.fromhex(v) for v in lines[f"moments{i}"].split()[2:]], np.float32).reshape(2, 7, 2)
         assert np.array_equal(ref.bits(got[0, :, 0]), ref.bits(a)) and np.array_equal(ref.bits(got[0, :, 1]), ref.bits(b))
         assert np.array_equal(ref.bits(got[1, :, 0]), ref.bits(c)) and np.array_equal(ref.bits(got[1, :, 1]), ref.bits(d))

@@ -146,7 +146,7 @@ def problem2(args, emit):
         mom = [ref.central_moments(m, norm_inf=True) for m in mhis]
         mu, eta = np.stack([r[0] for r in mom]), np.stack([r[1] for r in mom])
         for m in mhis:
-            ref.central_moments(ref.orc.mhi_energy(m))
+            ref.central_moments(ref.mhi_energy(m))
         acts, ppl = [v[4] for v in vids], [v[5] for v in vids]
         ref.naive_confusion(mu, acts)
         ref.naive_confusion(eta, acts)
