@@ -8,8 +8,9 @@ costs are integer sums of rounded terms by definition, so there the two agree at
 
 Both functions work per disparity on whole images (cumulative sums along y, then along x), which makes 1080 x 1920
 with 128 disparities a matter of seconds -- where the scalar C oracle is slow.  tests/test_stereo_ref.py checks them
-against the oracle byte for byte on small pairs; that ties the two references together but is no independent proof
-of the float contract on images that are not 8-bit-valued (these functions refuse such images).
+against the oracle byte for byte on small pairs; that ties the two references together.  These functions refuse images
+that are not 8-bit-valued: there the float contract is restated, order-exact in float32 and with float64 bounds, by
+tests/_stereo_f32_ref.py (tied to the oracle and to these functions by tests/test_stereo_f32_ref.py).
 """
 import numpy as np
 

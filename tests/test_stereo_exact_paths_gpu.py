@@ -1,7 +1,8 @@
 """disparitySSD's exact-sum dispatch (csrc/stereo_exact.hip) path by path.  Every case runs the call twice -- on a
 context that takes the exact-sum kernels when the pre-pass finds an 8-bit-valued pair (the default) and on one that never
 does (MICV_OPT_STEREO_EXACT = -1) -- and compares both byte for byte with an independent answer: the exact integer
-reference (tests/_stereo_ref.py) on 8-bit-valued pairs, the C oracle otherwise.
+reference (tests/_stereo_ref.py) on 8-bit-valued pairs, the order-exact float32 reference (tests/_stereo_f32_ref.py)
+otherwise (NaN and infinite pixels included); neither shares code with the C oracle.
 
   - every search-kernel instantiation stereo_exact_covers() can select, under 8 and 10 rows per float strip, on 8-bit pairs
     and on the same pairs with one pixel 0.5 (the float tiles that ride in the exact-sum launch), through a covering table
@@ -17,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
-import _oracle as orc
+import _stereo_f32_ref as fref
 import _stereo_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -60,12 +61,12 @@ def is_u8(img):
 
 
 def expected(left, right, rad, lo, hi, flags):
-    """The exact integer reference on 8-bit-valued pairs, the C oracle otherwise."""
+    """The exact integer reference on 8-bit-valued pairs, the order-exact float32 reference otherwise."""
     if is_u8(left) and is_u8(right):
         return ref.ssd_serial(left, right, rad, lo, hi) if flags & SERIAL else ref.ssd_cuda(left, right, rad, lo, hi, flags)
     if flags & SERIAL:
-        return orc.disparity_ssd_serial(left, right, rad, lo, hi)
-    return orc.disparity_ssd(left, right, rad, lo, hi, flags)
+        return fref.ssd_serial_f32(left, right, rad, lo, hi)
+    return fref.ssd_f32(left, right, rad, lo, hi, flags)
 
 
 def run_both(ctxs, left, right, rad, lo, hi, flags, pad=0):
@@ -231,7 +232,7 @@ BAD_FORMS = [(1, 0, -40, 10, 8), (5, 0, -70, 0, 8), (7, COLS_2R, -128, 127, 10)]
 def test_one_bad_pixel_anywhere(ctxs, rad, flags, lo, hi, rpw):
     """One pixel that is not an integer in 0..255 -- a fraction, 255.5, a negative, 256, a denormal, +-inf, NaN -- in
     either image: at each corner, in the last row of a partial 8-row strip, in the last column, and in a right-image
-    column reached only through clamping.  The call must equal the oracle (the float kernels did it); the next call on
+    column reached only through clamping.  The call must equal the float32 reference (the float kernels did it); the next call on
     the same context with a clean pair must equal the exact reference.  -0.0 is a legal 0: same bytes on either path."""
     set_rpw(ctxs, rpw)
     rows, cols = 21, 70  # strips 0..7, 8..15 and the partial 16..20
@@ -245,7 +246,7 @@ def test_one_bad_pixel_anywhere(ctxs, rad, flags, lo, hi, rpw):
         for side, y, x, plo, phi in places:
             left, right = u8_pair(rng, rows, cols, "noise")
             (left if side == 0 else right)[y, x] = bad
-            exp = orc.disparity_ssd(left, right, rad, plo, phi, flags)
+            exp = expected(left, right, rad, plo, phi, flags)
             check(ctxs, left, right, rad, plo, phi, flags, exp=exp, what=f"bad {bad} at {'LR'[side]}{(y, x)}")
             l2, r2 = u8_pair(rng, rows, cols, "noise")
             check(ctxs, l2, r2, rad, plo, phi, flags, what="clean after bad")
