@@ -1437,6 +1437,129 @@ int micv_ps6_track_display_seq_host(micv_pf *pf, const uint8_t *const *frames, i
                                     float bbox_w, float bbox_h, const double *box_color, const int *save, int nsave, int all_frames,
                                     uint8_t *const *out_frames, size_t ostride, micv_pf_state *states);
 
+/* ------------------------------------------------------------------ ps0 ------ */
+/* ps0 of the reference (ProblemSets/ps0_cpp/main.cpp) on the device.  OpenCV's behaviour is restated, PARITY UNPINNED
+ * ("ps0"); the statement of the contract is the host loops of shim/micv_ps0.hpp, and the `_dev` forms
+ * equal them byte for byte.  All images are 8-bit; strides are bytes per row, padding is never written.  `_dev` entries
+ * are asynchronous on `stream`, never synchronise the host and read every scalar they depend on from device memory;
+ * `_host` entries upload, run the same kernels and download (null stream).  rows * cols < 2^31.
+ *   cvRound  rounds halves to even and gives INT_MIN for NaN, +-inf and values outside int; sat (to u8) then gives 0. */
+typedef struct micv_ps0_stats {
+    double mean, stddev;
+    uint64_t sum, sqsum;
+    int32_t min, max;
+} micv_ps0_stats;
+/* cv::mixChannels on one image: dst channel k = src channel map[k] (map on the host, dcn entries, 1 <= scn, dcn <= 4; an
+ * entry outside the source is MICV_EINVAL).  swapRedBlue (main.cpp:17-23) is scn = dcn = 3, map {2, 1, 0};
+ * cv::extractChannel (:118, :123, :129, :169) is dcn = 1. */
+int micv_mix_channels_u8_dev(micv_ctx *ctx, const uint8_t *src, int rows, int cols, int scn, size_t sstride, const int *map, uint8_t *dst,
+                             int dcn, size_t dstride, micv_stream stream);
+int micv_mix_channels_u8_host(micv_ctx *ctx, const uint8_t *src, int rows, int cols, int scn, size_t sstride, const int *map, uint8_t *dst,
+                              int dcn, size_t dstride);
+/* pixelReplacement (:25-42): dst (rows2 x cols2) = img2 with the size x size square of img1 at (cols1 / 2 - size / 2,
+ * rows1 / 2 - size / 2) pasted at (cols2 / 2 - size / 2, rows2 / 2 - size / 2), integer division; the driver's size is 100.
+ * The images may differ in size and share `channels` (1..4).  A square that leaves either image is MICV_EINVAL (OpenCV
+ * throws there).  One launch; dst must not alias an input. */
+int micv_pixel_replacement_u8_dev(micv_ctx *ctx, const uint8_t *img1, int rows1, int cols1, size_t stride1, const uint8_t *img2, int rows2,
+                                  int cols2, size_t stride2, int channels, int size, uint8_t *dst, size_t dstride, micv_stream stream);
+int micv_pixel_replacement_u8_host(micv_ctx *ctx, const uint8_t *img1, int rows1, int cols1, size_t stride1, const uint8_t *img2, int rows2,
+                                   int cols2, size_t stride2, int channels, int size, uint8_t *dst, size_t dstride);
+/* cv::minMaxLoc + cv::meanStdDev (:135-138) of a single-channel image into a record (device for _dev): sum and sqsum are
+ * exact integers, mean = (double)sum * (1.0 / N), stddev = sqrt(max((double)sqsum * (1.0 / N) - mean * mean, 0.0)), unfused,
+ * N = rows * cols.  Two launches: one partial per workgroup (a thread sums at most 8192 pixels in 32 bits, everything
+ * after that in 64), then one workgroup adds the partials; no workgroup waits for another, and the result does not
+ * depend on the grid. */
+int micv_mean_stddev_u8_dev(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t stride, micv_ps0_stats *stats, micv_stream stream);
+int micv_mean_stddev_u8_host(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t stride, micv_ps0_stats *stats);
+/* doArithmeticOperations (:47-56): the four in-place steps of an 8-bit cv::Mat, each saturating before the next, one kernel:
+ *   t1 = sat(cvRound((double)p - mean)); t2 = sat(cvRound((float)t1 * a)), a = (float)(1.0 / stddev);
+ *   t3 = sat(cvRound((float)t2 * 10.f)); t4 = sat(cvRound((double)t3 + mean)).
+ * stddev = 0 runs as written: a = inf, 0 * inf = NaN -> 0.  _dev: mean_stddev points at {mean, stddev} on the device, the
+ * head of micv_ps0_stats; _host takes the two doubles. */
+int micv_ps0_arithmetic_u8_dev(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, const double *mean_stddev, uint8_t *dst,
+                               size_t dstride, micv_stream stream);
+int micv_ps0_arithmetic_u8_host(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, double mean, double stddev, uint8_t *dst,
+                                size_t dstride);
+/* `a -= b` on 8-bit images (:156-157): sat(a - b); the bytes of micv_add_weighted_*(a, 1, b, -1, 0). */
+int micv_subtract_sat_u8_dev(micv_ctx *ctx, const uint8_t *a, size_t astride, const uint8_t *b, size_t bstride, int rows, int cols, uint8_t *dst,
+                             size_t dstride, micv_stream stream);
+int micv_subtract_sat_u8_host(micv_ctx *ctx, const uint8_t *a, size_t astride, const uint8_t *b, size_t bstride, int rows, int cols, uint8_t *dst,
+                              size_t dstride);
+/* addGaussianNoise (:64-79) as the reference wrote it: `noise` is a float plane holding z * sigma + mean as
+ * micv_cv_randn_f32_host draws it; n = sat_s8(cvRound(noise)) (cv::randn into CV_8SC1; a NaN sample is -128), and
+ * out = max(0, clamp(min(p, 127) + n, -128, 127)).  The clip of the image at 127 is the reference's
+ * image.convertTo(output, CV_8SC1) (:76): a bright pixel loses its value before the noise is added. */
+int micv_add_noise_s8_u8_dev(micv_ctx *ctx, const uint8_t *src, size_t sstride, const float *noise, size_t nstride, int rows, int cols,
+                             uint8_t *dst, size_t dstride, micv_stream stream);
+int micv_add_noise_s8_u8_host(micv_ctx *ctx, const uint8_t *src, size_t sstride, const float *noise, size_t nstride, int rows, int cols,
+                              uint8_t *dst, size_t dstride);
+/* main.cpp:110-171 as one call, THREE launches: image1 and image2 are B, G, R.  Pass one reads image1 once, writes
+ * `swapped` and the green and red planes and reduces green's partials; a paste launch makes `replaced` (rows2 x cols2) from
+ * the red channels of the two images; pass two forms mean and stddev from the integer sums in its prologue, writes the
+ * record, and writes the arithmetic image, green translated by (-2, 0) with zero fill (the bytes of micv_warp_affine_* with
+ * m = {1, 0, -2, 0, 1, 0}, flags 0), green - translated, and the noisy green and blue planes (blue is read from image1).
+ * planes: seven rows1 x cols1 planes plane_pitch bytes apart, pstride bytes per row: green, red, arithmetic, translated,
+ * difference, noisy green, noisy blue.  Every output equals the separate calls above byte for byte.  _host draws green's
+ * noise plane, then blue's, from one generator (micv_cv_randn_f32_host on *rng_state, which comes back advanced). */
+int micv_ps0_run_dev(micv_ctx *ctx, const uint8_t *image1, int rows1, int cols1, size_t stride1, const uint8_t *image2, int rows2, int cols2,
+                     size_t stride2, int size, const float *noise_green, const float *noise_blue, size_t nstride, uint8_t *swapped,
+                     size_t wstride, uint8_t *planes, size_t pstride, size_t plane_pitch, uint8_t *replaced, size_t rstride,
+                     micv_ps0_stats *stats, micv_stream stream);
+int micv_ps0_run_host(micv_ctx *ctx, const uint8_t *image1, int rows1, int cols1, size_t stride1, const uint8_t *image2, int rows2, int cols2,
+                      size_t stride2, int size, uint64_t *rng_state, float noise_mean, float noise_sigma, uint8_t *swapped, size_t wstride,
+                      uint8_t *planes, size_t pstride, size_t plane_pitch, uint8_t *replaced, size_t rstride, micv_ps0_stats *stats);
+
+/* ------------------------------------------------------------------ ps3: driver ------ */
+/* What runProblem2 and runExtraCredit (ProblemSets/ps3_cpp/src/Solution.cpp:323-481) do after the fundamental matrix:
+ * drawEpipolarLines (:122-158) calls cv::line(img, Point2f(P_iL), Point2f(P_iR), color) for every epipolar line (:153-156).
+ * OpenCV's source is not available to this repository, so its drawing is restated, PARITY UNPINNED (DESIGN.md section 2,
+ * "ps3 driver"); the statement of the contract is the host loop micv_ps3::line_wide (shim/micv_ps3.hpp), and the device
+ * forms equal it byte for byte.  Every `_dev` entry is asynchronous on `stream`, reads the end points on the device and
+ * never synchronises; MICV_EINVAL is returned before anything is enqueued.
+ * Images: 8-bit, 1, 3 or 4 interleaved channels, rows and cols in 1 .. 32768, `stride` bytes per row (>= cols *
+ * channels, < 2^32); only the bytes of a painted pixel are written, padding never.
+ * Colours: as for micv_draw_rectangle_*: four doubles; byte k of a painted pixel is saturate(nearbyint(color[k])).
+ * End points (Point2f -> Point): each coordinate through cvRound, which rounds halves to even (2.5 -> 2, 3.5 -> 4) and
+ *   gives INT_MIN for NaN, +-inf and every value outside int; INT_MIN then takes part as a number.
+ * Segment: the walk of micv_viz::line (shim/micv_viz.hpp: the ends swapped when p1.x > p2.x, major = max(dx, |dy|) with
+ *   the tie going to x, major + 1 steps, err = major - 2 minor) WITH ITS INTEGERS AS WIDE AS THEY NEED TO BE.  The walk in
+ *   `int` overflows from |dx| or |dy| >= 2^30 on; the end points of a near-vertical epipolar line lie at |y| ~ 2^31.
+ *   Here the result is exact for every pair of int32 end points: step i sits at the major coordinate start +- i and the
+ *   minor coordinate start +- (2 minor i + major - 1) div (2 major), in unbounded integers.  Pixels outside the image
+ *   are dropped.  All segments of a call share the colour, so the order of drawing does not matter.
+ * One launch: a wave per segment, a lane per step whose major coordinate is in the image (at most max(rows, cols)).
+ * 0 <= n <= 2^28; n = 0 is a no-op.  _host: upload, the same launch, download, sync (null stream). */
+/* segments: n x {x1, y1, x2, y2} f32 (device for _dev). */
+int micv_draw_segments_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *segments, int n,
+                           const double *color, micv_stream stream);
+int micv_draw_segments_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *segments, int n,
+                            const double *color);
+/* drawEpipolarLines from the [n][6] block of micv_epipolar_endpoints_* (P_iL then P_iR, three floats each): the segment
+ * (e[0], e[1]) -> (e[3], e[4]) for every line; e[2] and e[5] are not read.  A vertical epipolar line (l_1 = 0) meets
+ * neither the left nor the right border: its end points are NaN / +-inf, both x become INT_MIN, both ends sit on one
+ * side of the image and the image stays untouched (the reference hands the same values to cv::line). */
+int micv_draw_epipolar_lines_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *endpoints,
+                                 int n, const double *color, micv_stream stream);
+int micv_draw_epipolar_lines_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *endpoints,
+                                  int n, const double *color);
+/* Part c of runProblem2 and part e of runExtraCredit (:341-363, :459-475) as one call: F 3 x 3 (row-major; device for
+ * _dev, where a chain left it), ptsA and ptsB n x {x, y} as micv_epipolar_endpoints_* takes them, 1 <= n <= 2^27.  outA
+ * receives imgA with the lines of image B's points (side 0), outB imgB with the lines of image A's points (side 1); the
+ * two pictures may differ in size and share `channels`.  out may be the picture itself (then ostride == stride); a
+ * separate out receives a copy of the picture first and the picture stays as it is.  ONE launch over (image, line): a
+ * wave computes the end points of its line with the device function of micv_epipolar_endpoints_dev and walks them at
+ * once, so nothing but F and the points is read.  flags: MICV_GEOM_F64, passed through to the end points.  endpoints
+ * (or NULL): [2][n][6], side 0 then side 1, the bits of micv_epipolar_endpoints_*.  The bytes equal
+ * micv_epipolar_endpoints_* followed by micv_draw_epipolar_lines_* on each image. */
+int micv_ps3_epipolar_display_dev(micv_ctx *ctx, const float *F, const float *ptsA, const float *ptsB, int n, const uint8_t *imgA,
+                                  size_t astride, int rowsA, int colsA, const uint8_t *imgB, size_t bstride, int rowsB, int colsB,
+                                  int channels, uint32_t flags, const double *color, uint8_t *outA, size_t oastride, uint8_t *outB,
+                                  size_t obstride, float *endpoints, micv_stream stream);
+int micv_ps3_epipolar_display_host(micv_ctx *ctx, const float *F, const float *ptsA, const float *ptsB, int n, const uint8_t *imgA,
+                                   size_t astride, int rowsA, int colsA, const uint8_t *imgB, size_t bstride, int rowsB, int colsB,
+                                   int channels, uint32_t flags, const double *color, uint8_t *outA, size_t oastride, uint8_t *outB,
+                                   size_t obstride, float *endpoints);
+
 #ifdef __cplusplus
 }
 #endif

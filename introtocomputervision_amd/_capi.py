@@ -310,6 +310,31 @@ SIGNATURES = {
     "micv_camera_center_host": (i32, [vp, vp, i32, u32, vp]),
     "micv_geom_trial_indices": (i32, [vp, i64, i32, vp]),
     "micv_geom_sample_indices_dev": (i32, [vp, C.c_uint64, i32, i32, i64, vp, vp]),
+    # ps0
+    "micv_mix_channels_u8_dev": (i32, [vp, vp, i32, i32, i32, sz, C.POINTER(i32), vp, i32, sz, vp]),
+    "micv_mix_channels_u8_host": (i32, [vp, vp, i32, i32, i32, sz, C.POINTER(i32), vp, i32, sz]),
+    "micv_pixel_replacement_u8_dev": (i32, [vp, vp, i32, i32, sz, vp, i32, i32, sz, i32, i32, vp, sz, vp]),
+    "micv_pixel_replacement_u8_host": (i32, [vp, vp, i32, i32, sz, vp, i32, i32, sz, i32, i32, vp, sz]),
+    "micv_mean_stddev_u8_dev": (i32, [vp, vp, i32, i32, sz, vp, vp]),
+    "micv_mean_stddev_u8_host": (i32, [vp, vp, i32, i32, sz, vp]),
+    "micv_ps0_arithmetic_u8_dev": (i32, [vp, vp, i32, i32, sz, vp, vp, sz, vp]),
+    "micv_ps0_arithmetic_u8_host": (i32, [vp, vp, i32, i32, sz, f64, f64, vp, sz]),
+    "micv_subtract_sat_u8_dev": (i32, [vp, vp, sz, vp, sz, i32, i32, vp, sz, vp]),
+    "micv_subtract_sat_u8_host": (i32, [vp, vp, sz, vp, sz, i32, i32, vp, sz]),
+    "micv_add_noise_s8_u8_dev": (i32, [vp, vp, sz, vp, sz, i32, i32, vp, sz, vp]),
+    "micv_add_noise_s8_u8_host": (i32, [vp, vp, sz, vp, sz, i32, i32, vp, sz]),
+    "micv_ps0_run_dev": (i32, [vp, vp, i32, i32, sz, vp, i32, i32, sz, i32, vp, vp, sz, vp, sz, vp, sz, sz, vp, sz, vp, vp]),
+    "micv_ps0_run_host": (i32, [vp, vp, i32, i32, sz, vp, i32, i32, sz, i32, C.POINTER(C.c_uint64), f32, f32, vp, sz, vp, sz, sz, vp, sz,
+                                vp]),
+    # ps3 driver
+    "micv_draw_segments_dev": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, vp, vp]),
+    "micv_draw_segments_host": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, vp]),
+    "micv_draw_epipolar_lines_dev": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, vp, vp]),
+    "micv_draw_epipolar_lines_host": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, vp]),
+    "micv_ps3_epipolar_display_dev": (i32, [vp, vp, vp, vp, i32, vp, sz, i32, i32, vp, sz, i32, i32, i32, u32, vp, vp, sz, vp, sz,
+                                            vp, vp]),
+    "micv_ps3_epipolar_display_host": (i32, [vp, vp, vp, vp, i32, vp, sz, i32, i32, vp, sz, i32, i32, i32, u32, vp, vp, sz, vp, sz,
+                                             vp]),
 }
 
 MISSING = []

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "epipolar.hpp"
 
 struct micv_ransac_rng {  // ransac.hip
     std::mt19937 eng;
@@ -529,46 +530,16 @@ __global__ void fnorm_compose_kernel(const R *__restrict__ Tab, const R *__restr
     }
 }
 
-template <typename R>
-__device__ inline void cross3(const R *a, const R *b, R *c) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 // Solution.cpp:343-362 and :124-163: the epipolar line of each point and its intersections with
-// the left and right image borders, each scaled by the reciprocal of its third coordinate.
+// the left and right image borders, each scaled by the reciprocal of its third coordinate (epipolar.hpp).
 template <typename R>
 __global__ __launch_bounds__(256) void epipolar_kernel(const float *__restrict__ F, const float *__restrict__ pts, int n,
                                                        int side, int rows, int cols, float *__restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const R rm1 = (R)(rows - 1), cm1 = (R)(cols - 1);
-    const R ul[3] = {0, 0, 1}, bl[3] = {0, rm1, 1}, ur[3] = {cm1, 0, 1}, br[3] = {cm1, rm1, 1};
-    R IL[3], IR[3], l[3], PL[3], PR[3];
-    cross3<R>(ul, bl, IL);
-    cross3<R>(ur, br, IR);
-    const double x = pts[2 * (size_t)i], y = pts[2 * (size_t)i + 1];
-    for (int c = 0; c < 3; c++) {
-        double s;
-        if (side == 0) {  // (p^T F)^T
-            s = x * (double)F[c];
-            s = s + y * (double)F[3 + c];
-            s = s + 1.0 * (double)F[6 + c];
-        } else {  // F p
-            s = (double)F[3 * c] * x;
-            s = s + (double)F[3 * c + 1] * y;
-            s = s + (double)F[3 * c + 2] * 1.0;
-        }
-        l[c] = (R)s;
-    }
-    cross3<R>(l, IL, PL);
-    cross3<R>(l, IR, PR);
-    const R rl = (R)(1.0 / (double)PL[2]), rr = (R)(1.0 / (double)PR[2]);
-    for (int c = 0; c < 3; c++) {
-        out[6 * (size_t)i + c] = (float)(PL[c] * rl);
-        out[6 * (size_t)i + 3 + c] = (float)(PR[c] * rr);
-    }
+    float e[6];
+    epipolar_endpoints<R>(F, pts[2 * (size_t)i], pts[2 * (size_t)i + 1], side, rows, cols, e);
+    for (int c = 0; c < 6; c++) out[6 * (size_t)i + c] = e[c];
 }
 
 // Solution.cpp:320-326: -Q^-1 m4.  Q^-1 is the closed form ransac.hip restates for a 3 x 3 CV_32F
