@@ -38,6 +38,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include <mutex>
 #include <vector>
 
+#include "host_io.hpp"
 #include "kernels.hpp"
 
 namespace micv {
@@ -630,45 +631,16 @@ int micv_lk_flow_pyr_rowshard_host(micv_ctx *ctx, micv_comm *comm, const float *
     MICV_REQUIRE(ctx && comm && prev && next && u && v, "micv_lk_flow_pyr_rowshard_host: null argument");
     MICV_REQUIRE(rows > 0 && cols > 0 && stride_ok(stride, cols, 4) && stride_ok(ostride, cols, 4),
                  "micv_lk_flow_pyr_rowshard_host: bad size / stride");
-    MICV_HIP(hipSetDevice(ctx->device));
+    HostCall h(ctx, "micv_lk_flow_pyr_rowshard_host");
+    if (!h.ok()) return h.finish();
     const size_t rb = (size_t)cols * 4, n = rb * rows;
-    // frames and full-size outputs on the device: the context's cached blocks, as every other `_host` entry point
-    // (host_api.hip) -- a repeated call of the same shape does no hipMalloc / hipFree (this one did four per
-    // call).  The communicator's own block is in use by the driver.
     MICV_REQUIRE(comm->device == ctx->device, "micv_lk_flow_pyr_rowshard_host: communicator and context are on different devices");
-    float *dp = static_cast<float *>(ctx->io_acquire(n)), *dn = static_cast<float *>(ctx->io_acquire(n));
-    float *du = static_cast<float *>(ctx->io_acquire(n)), *dv = static_cast<float *>(ctx->io_acquire(n));
-    hipStream_t s = nullptr;  // the null stream: every call of this entry point is synchronous, like the reference's
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(s);  // nothing may still use a block that goes back to the cache
-        for (float *p : {dp, dn, du, dv})
-            if (p) ctx->io_release(p);
-    };
-    if (!dp || !dn || !du || !dv) {
-        cleanup();
-        set_error("micv_lk_flow_pyr_rowshard_host: device allocation failed");
-        return MICV_ENOMEM;
-    }
-#define MICV_RS(expr)                 \
-    do {                              \
-        const int rc_ = (expr);       \
-        if (rc_ != MICV_OK) {         \
-            cleanup();                \
-            return rc_;               \
-        }                             \
-    } while (0)
-#define MICV_RS_HIP(expr)                                                          \
-    do {                                                                           \
-        const hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess) {                                                    \
-            set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-            cleanup();                                                             \
-            return MICV_EHIP;                                                      \
-        }                                                                          \
-    } while (0)
-    MICV_RS_HIP(hipMemcpy2DAsync(dp, rb, prev, stride, rb, rows, hipMemcpyHostToDevice, s));
-    MICV_RS_HIP(hipMemcpy2DAsync(dn, rb, next, stride, rb, rows, hipMemcpyHostToDevice, s));
-    MICV_RS(micv_lk_flow_pyr_rowshard_dev(ctx, comm, dp, dn, 1, 0, rows, cols, rb, win, levels, du, dv, 0, rb, s));
+    // frames and full-size outputs on the device: the context's cached blocks, as every other `_host` entry point
+    // (host_io.hpp).  The communicator's own block is in use by the driver.
+    float *dp = h.up<float>(prev, stride, rb, rows), *dn = h.up<float>(next, stride, rb, rows);
+    float *du = h.alloc<float>(n), *dv = h.alloc<float>(n);
+    if (!h.ok()) return h.finish();
+    MICV_TRY(micv_lk_flow_pyr_rowshard_dev(ctx, comm, dp, dn, 1, 0, rows, cols, rb, win, levels, du, dv, 0, rb, h.s));
     // every rank's band to every rank: the cv::Mat caller gets whole fields back (lk::calcOpticalFlowPyr's contract)
     if (comm->world > 1) {
         RowPlan plan;
@@ -680,23 +652,18 @@ int micv_lk_flow_pyr_rowshard_host(micv_ctx *ctx, micv_comm *comm, const float *
             plan.band(0, g, &a, &b);
             const size_t cnt = (size_t)(b - a) * cols;
             if (cnt == 0) continue;
-            nr = r->Broadcast(du + (size_t)a * cols, du + (size_t)a * cols, cnt, ncclFloat32, g, comm->comm, s);
-            if (nr == ncclSuccess) nr = r->Broadcast(dv + (size_t)a * cols, dv + (size_t)a * cols, cnt, ncclFloat32, g, comm->comm, s);
+            nr = r->Broadcast(du + (size_t)a * cols, du + (size_t)a * cols, cnt, ncclFloat32, g, comm->comm, h.s);
+            if (nr == ncclSuccess) nr = r->Broadcast(dv + (size_t)a * cols, dv + (size_t)a * cols, cnt, ncclFloat32, g, comm->comm, h.s);
         }
         const ncclResult_t ne = r->GroupEnd();
         if (nr != ncclSuccess || ne != ncclSuccess) {
             set_error("micv_lk_flow_pyr_rowshard_host: gathering the bands -> %s", r->GetErrorString(nr != ncclSuccess ? nr : ne));
-            cleanup();
             return MICV_EHIP;
         }
     }
-    MICV_RS_HIP(hipMemcpy2DAsync(u, ostride, du, rb, rb, rows, hipMemcpyDeviceToHost, s));
-    MICV_RS_HIP(hipMemcpy2DAsync(v, ostride, dv, rb, rb, rows, hipMemcpyDeviceToHost, s));
-    MICV_RS_HIP(hipStreamSynchronize(s));
-#undef MICV_RS
-#undef MICV_RS_HIP
-    cleanup();
-    return MICV_OK;
+    h.down(u, ostride, du, rb, rows);
+    h.down(v, ostride, dv, rb, rows);
+    return h.finish();
 }
 
 }  // extern "C"

@@ -103,7 +103,7 @@ struct micv_ctx {
     static constexpr size_t kMaxProfPairs = 4096;  // per level; recording stops there until a reset
     unsigned long long *stamps = nullptr;  // 16 device counters (micv_profile_lk_phases)
     int prof_pairs = 0;                    // frame pairs per profiled level launch
-    // Device blocks of the host-pointer entry points (host_api.hip), kept between calls so that a
+    // Device blocks of the host-pointer entry points (HostCall, host_io.hpp), kept between calls so that a
     // repeated call of the same shape does no hipMalloc / hipFree.  Freed with the context.
     struct IoBlock {
         void *p;

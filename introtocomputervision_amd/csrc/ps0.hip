@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "host_io.hpp"
 
 namespace micv {
 namespace {
@@ -235,38 +236,6 @@ bool squares(int r1, int c1, int r2, int c2, int size, Paste *p) {
            p->by + size <= r2;
 }
 
-// device copies of host images, released on every way out after everything enqueued has finished
-struct HostIO {
-    std::vector<void *> bufs;
-    bool ok = true;
-    ~HostIO() {
-        (void)hipStreamSynchronize(nullptr);
-        for (void *b : bufs) (void)hipFree(b);
-    }
-    uint8_t *alloc(size_t bytes) {
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) {
-            ok = false;
-            return nullptr;
-        }
-        bufs.push_back(p);
-        return static_cast<uint8_t *>(p);
-    }
-    uint8_t *up(const void *h, size_t hstride, size_t rb, int rows) {
-        uint8_t *d = alloc(rb * rows);
-        if (d && hipMemcpy2DAsync(d, rb, h, hstride, rb, rows, hipMemcpyHostToDevice, nullptr) != hipSuccess) ok = false;
-        return d;
-    }
-    void down(void *h, size_t hstride, const void *d, size_t rb, int rows) {
-        if (hipMemcpy2DAsync(h, hstride, d, rb, rb, rows, hipMemcpyDeviceToHost, nullptr) != hipSuccess) ok = false;
-    }
-    int finish(const char *fn) {
-        if (hipStreamSynchronize(nullptr) != hipSuccess) ok = false;
-        if (!ok) set_error("%s: an allocation or a copy failed", fn);
-        return ok ? MICV_OK : MICV_EHIP;
-    }
-};
-
 }  // namespace
 }  // namespace micv
 
@@ -295,13 +264,13 @@ int micv_mix_channels_u8_host(micv_ctx *ctx, const uint8_t *src, int rows, int c
     MICV_REQUIRE(ctx && scn >= 1 && scn <= 4 && dcn >= 1 && dcn <= 4 && plane_ok(src, rows, cols, scn, sstride) &&
                      plane_ok(dst, rows, cols, dcn, dstride),
                  "micv_mix_channels_u8_host: bad argument");
-    MICV_HIP(hipSetDevice(ctx->device));
-    HostIO io;
+    HostCall h(ctx, "micv_mix_channels_u8_host");
     const size_t sb = (size_t)cols * scn, db = (size_t)cols * dcn;
-    uint8_t *s = io.up(src, sstride, sb, rows), *d = io.alloc(db * rows);
-    if (io.ok) MICV_TRY(micv_mix_channels_u8_dev(ctx, s, rows, cols, scn, sb, map, d, dcn, db, nullptr));
-    if (io.ok) io.down(dst, dstride, d, db, rows);
-    return io.finish("micv_mix_channels_u8_host");
+    uint8_t *s = h.up<uint8_t>(src, sstride, sb, rows), *d = h.alloc<uint8_t>(db * rows);
+    if (!h.ok()) return h.finish();
+    MICV_TRY(micv_mix_channels_u8_dev(ctx, s, rows, cols, scn, sb, map, d, dcn, db, h.s));
+    h.down(dst, dstride, d, db, rows);
+    return h.finish();
 }
 
 int micv_pixel_replacement_u8_dev(micv_ctx *ctx, const uint8_t *img1, int rows1, int cols1, size_t stride1, const uint8_t *img2, int rows2,
@@ -328,13 +297,13 @@ int micv_pixel_replacement_u8_host(micv_ctx *ctx, const uint8_t *img1, int rows1
                  "micv_pixel_replacement_u8_host: bad argument");
     Paste q{};
     MICV_REQUIRE(squares(rows1, cols1, rows2, cols2, size, &q), "micv_pixel_replacement_u8_host: the %d x %d square leaves an image", size, size);
-    MICV_HIP(hipSetDevice(ctx->device));
-    HostIO io;
+    HostCall h(ctx, "micv_pixel_replacement_u8_host");
     const size_t b1 = (size_t)cols1 * channels, b2 = (size_t)cols2 * channels;
-    uint8_t *a = io.up(img1, stride1, b1, rows1), *b = io.up(img2, stride2, b2, rows2), *d = io.alloc(b2 * rows2);
-    if (io.ok) MICV_TRY(micv_pixel_replacement_u8_dev(ctx, a, rows1, cols1, b1, b, rows2, cols2, b2, channels, size, d, b2, nullptr));
-    if (io.ok) io.down(dst, dstride, d, b2, rows2);
-    return io.finish("micv_pixel_replacement_u8_host");
+    uint8_t *a = h.up<uint8_t>(img1, stride1, b1, rows1), *b = h.up<uint8_t>(img2, stride2, b2, rows2), *d = h.alloc<uint8_t>(b2 * rows2);
+    if (!h.ok()) return h.finish();
+    MICV_TRY(micv_pixel_replacement_u8_dev(ctx, a, rows1, cols1, b1, b, rows2, cols2, b2, channels, size, d, b2, h.s));
+    h.down(dst, dstride, d, b2, rows2);
+    return h.finish();
 }
 
 int micv_mean_stddev_u8_dev(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t stride, micv_ps0_stats *stats, micv_stream stream) {
@@ -354,12 +323,13 @@ int micv_mean_stddev_u8_dev(micv_ctx *ctx, const uint8_t *src, int rows, int col
 
 int micv_mean_stddev_u8_host(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t stride, micv_ps0_stats *stats) {
     MICV_REQUIRE(ctx && stats && plane_ok(src, rows, cols, 1, stride), "micv_mean_stddev_u8_host: bad argument (rows * cols < 2^31)");
-    MICV_HIP(hipSetDevice(ctx->device));
-    HostIO io;
-    uint8_t *s = io.up(src, stride, (size_t)cols, rows), *d = io.alloc(sizeof(micv_ps0_stats));
-    if (io.ok) MICV_TRY(micv_mean_stddev_u8_dev(ctx, s, rows, cols, (size_t)cols, reinterpret_cast<micv_ps0_stats *>(d), nullptr));
-    if (io.ok && hipMemcpyAsync(stats, d, sizeof(micv_ps0_stats), hipMemcpyDeviceToHost, nullptr) != hipSuccess) io.ok = false;
-    return io.finish("micv_mean_stddev_u8_host");
+    HostCall h(ctx, "micv_mean_stddev_u8_host");
+    uint8_t *s = h.up<uint8_t>(src, stride, (size_t)cols, rows);
+    micv_ps0_stats *d = h.alloc<micv_ps0_stats>(sizeof(micv_ps0_stats));
+    if (!h.ok()) return h.finish();
+    MICV_TRY(micv_mean_stddev_u8_dev(ctx, s, rows, cols, (size_t)cols, d, h.s));
+    h.down(stats, d, sizeof(micv_ps0_stats));
+    return h.finish();
 }
 
 int micv_ps0_arithmetic_u8_dev(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, const double *mean_stddev, uint8_t *dst,
@@ -375,13 +345,14 @@ int micv_ps0_arithmetic_u8_dev(micv_ctx *ctx, const uint8_t *src, int rows, int 
 int micv_ps0_arithmetic_u8_host(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t sstride, double mean, double stddev, uint8_t *dst,
                                 size_t dstride) {
     MICV_REQUIRE(ctx && plane_ok(src, rows, cols, 1, sstride) && plane_ok(dst, rows, cols, 1, dstride), "micv_ps0_arithmetic_u8_host: bad argument");
-    MICV_HIP(hipSetDevice(ctx->device));
-    HostIO io;
+    HostCall h(ctx, "micv_ps0_arithmetic_u8_host");
     const double ms[2] = {mean, stddev};
-    uint8_t *s = io.up(src, sstride, (size_t)cols, rows), *d = io.alloc((size_t)cols * rows), *m = io.up(ms, 16, 16, 1);
-    if (io.ok) MICV_TRY(micv_ps0_arithmetic_u8_dev(ctx, s, rows, cols, (size_t)cols, reinterpret_cast<const double *>(m), d, (size_t)cols, nullptr));
-    if (io.ok) io.down(dst, dstride, d, (size_t)cols, rows);
-    return io.finish("micv_ps0_arithmetic_u8_host");
+    uint8_t *s = h.up<uint8_t>(src, sstride, (size_t)cols, rows), *d = h.alloc<uint8_t>((size_t)cols * rows);
+    double *m = h.up<double>(ms, 16);
+    if (!h.ok()) return h.finish();
+    MICV_TRY(micv_ps0_arithmetic_u8_dev(ctx, s, rows, cols, (size_t)cols, m, d, (size_t)cols, h.s));
+    h.down(dst, dstride, d, (size_t)cols, rows);
+    return h.finish();
 }
 
 int micv_subtract_sat_u8_dev(micv_ctx *ctx, const uint8_t *a, size_t astride, const uint8_t *b, size_t bstride, int rows, int cols, uint8_t *dst,
@@ -398,13 +369,13 @@ int micv_subtract_sat_u8_host(micv_ctx *ctx, const uint8_t *a, size_t astride, c
                               size_t dstride) {
     MICV_REQUIRE(ctx && plane_ok(a, rows, cols, 1, astride) && plane_ok(b, rows, cols, 1, bstride) && plane_ok(dst, rows, cols, 1, dstride),
                  "micv_subtract_sat_u8_host: bad argument");
-    MICV_HIP(hipSetDevice(ctx->device));
-    HostIO io;
+    HostCall h(ctx, "micv_subtract_sat_u8_host");
     const size_t rb = (size_t)cols;
-    uint8_t *da = io.up(a, astride, rb, rows), *db = io.up(b, bstride, rb, rows), *d = io.alloc(rb * rows);
-    if (io.ok) MICV_TRY(micv_subtract_sat_u8_dev(ctx, da, rb, db, rb, rows, cols, d, rb, nullptr));
-    if (io.ok) io.down(dst, dstride, d, rb, rows);
-    return io.finish("micv_subtract_sat_u8_host");
+    uint8_t *da = h.up<uint8_t>(a, astride, rb, rows), *db = h.up<uint8_t>(b, bstride, rb, rows), *d = h.alloc<uint8_t>(rb * rows);
+    if (!h.ok()) return h.finish();
+    MICV_TRY(micv_subtract_sat_u8_dev(ctx, da, rb, db, rb, rows, cols, d, rb, h.s));
+    h.down(dst, dstride, d, rb, rows);
+    return h.finish();
 }
 
 int micv_add_noise_s8_u8_dev(micv_ctx *ctx, const uint8_t *src, size_t sstride, const float *noise, size_t nstride, int rows, int cols,
@@ -422,13 +393,14 @@ int micv_add_noise_s8_u8_host(micv_ctx *ctx, const uint8_t *src, size_t sstride,
                               uint8_t *dst, size_t dstride) {
     MICV_REQUIRE(ctx && plane_ok(src, rows, cols, 1, sstride) && plane_ok(noise, rows, cols, 4, nstride) && plane_ok(dst, rows, cols, 1, dstride),
                  "micv_add_noise_s8_u8_host: bad argument");
-    MICV_HIP(hipSetDevice(ctx->device));
-    HostIO io;
+    HostCall h(ctx, "micv_add_noise_s8_u8_host");
     const size_t rb = (size_t)cols;
-    uint8_t *s = io.up(src, sstride, rb, rows), *z = io.up(noise, nstride, rb * 4, rows), *d = io.alloc(rb * rows);
-    if (io.ok) MICV_TRY(micv_add_noise_s8_u8_dev(ctx, s, rb, reinterpret_cast<const float *>(z), rb * 4, rows, cols, d, rb, nullptr));
-    if (io.ok) io.down(dst, dstride, d, rb, rows);
-    return io.finish("micv_add_noise_s8_u8_host");
+    uint8_t *s = h.up<uint8_t>(src, sstride, rb, rows), *d = h.alloc<uint8_t>(rb * rows);
+    float *z = h.up<float>(noise, nstride, rb * 4, rows);
+    if (!h.ok()) return h.finish();
+    MICV_TRY(micv_add_noise_s8_u8_dev(ctx, s, rb, z, rb * 4, rows, cols, d, rb, h.s));
+    h.down(dst, dstride, d, rb, rows);
+    return h.finish();
 }
 
 int micv_ps0_run_dev(micv_ctx *ctx, const uint8_t *image1, int rows1, int cols1, size_t stride1, const uint8_t *image2, int rows2, int cols2,
@@ -479,22 +451,19 @@ int micv_ps0_run_host(micv_ctx *ctx, const uint8_t *image1, int rows1, int cols1
     const size_t n = (size_t)rows1 * cols1, rb = (size_t)cols1;
     MICV_TRY(micv_cv_randn_f32_host(rng_state, noise_mean, noise_sigma, rows1, cols1, noise.data(), rb * 4));
     MICV_TRY(micv_cv_randn_f32_host(rng_state, noise_mean, noise_sigma, rows1, cols1, noise.data() + n, rb * 4));
-    MICV_HIP(hipSetDevice(ctx->device));
-    HostIO io;
-    uint8_t *d1 = io.up(image1, stride1, rb * 3, rows1), *d2 = io.up(image2, stride2, (size_t)cols2 * 3, rows2);
-    uint8_t *dn = io.up(noise.data(), 2 * n * 4, 2 * n * 4, 1);
-    uint8_t *dw = io.alloc(3 * n), *dp = io.alloc(7 * n), *dr = io.alloc((size_t)rows2 * cols2), *ds = io.alloc(sizeof(micv_ps0_stats));
-    if (io.ok)
-        MICV_TRY(micv_ps0_run_dev(ctx, d1, rows1, cols1, rb * 3, d2, rows2, cols2, (size_t)cols2 * 3, size, reinterpret_cast<const float *>(dn),
-                                  reinterpret_cast<const float *>(dn) + n, rb * 4, dw, rb * 3, dp, rb, n, dr, (size_t)cols2,
-                                  reinterpret_cast<micv_ps0_stats *>(ds), nullptr));
-    if (io.ok) {
-        io.down(swapped, wstride, dw, rb * 3, rows1);
-        for (int k = 0; k < 7; k++) io.down(planes + k * plane_pitch, pstride, dp + k * n, rb, rows1);
-        io.down(replaced, rstride, dr, (size_t)cols2, rows2);
-        if (hipMemcpyAsync(stats, ds, sizeof(micv_ps0_stats), hipMemcpyDeviceToHost, nullptr) != hipSuccess) io.ok = false;
-    }
-    return io.finish("micv_ps0_run_host");
+    HostCall h(ctx, "micv_ps0_run_host");
+    uint8_t *d1 = h.up<uint8_t>(image1, stride1, rb * 3, rows1), *d2 = h.up<uint8_t>(image2, stride2, (size_t)cols2 * 3, rows2);
+    float *dn = h.up<float>(noise.data(), 2 * n * 4);
+    uint8_t *dw = h.alloc<uint8_t>(3 * n), *dp = h.alloc<uint8_t>(7 * n), *dr = h.alloc<uint8_t>((size_t)rows2 * cols2);
+    micv_ps0_stats *ds = h.alloc<micv_ps0_stats>(sizeof(micv_ps0_stats));
+    if (!h.ok()) return h.finish();
+    MICV_TRY(micv_ps0_run_dev(ctx, d1, rows1, cols1, rb * 3, d2, rows2, cols2, (size_t)cols2 * 3, size, dn, dn + n, rb * 4, dw, rb * 3, dp, rb,
+                              n, dr, (size_t)cols2, ds, h.s));
+    h.down(swapped, wstride, dw, rb * 3, rows1);
+    for (int k = 0; k < 7; k++) h.down(planes + k * plane_pitch, pstride, dp + k * n, rb, rows1);
+    h.down(replaced, rstride, dr, (size_t)cols2, rows2);
+    h.down(stats, ds, sizeof(micv_ps0_stats));
+    return h.finish();
 }
 
 }  // extern "C"

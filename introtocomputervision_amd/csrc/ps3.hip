@@ -13,6 +13,7 @@
 #include <initializer_list>
 
 #include "common.hpp"
+#include "host_io.hpp"
 #include "epipolar.hpp"
 #include "ps3_lane.hpp"
 
@@ -98,29 +99,17 @@ int launch_segments(micv_ctx *ctx, uint8_t *img, int rows, int cols, int ch, siz
 }
 
 // upload, the same launch, download, synchronise; the padding of the caller's rows is never read or written
-int segments_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, int ch, size_t stride, const float *p, int n, int pitch, int off2,
+int segments_host(const char *fn, micv_ctx *ctx, uint8_t *img, int rows, int cols, int ch, size_t stride, const float *p, int n, int pitch, int off2,
                   const double *color) {
     if (n == 0) return MICV_OK;
-    MICV_HIP(hipSetDevice(ctx->device));
-    struct Scope {  // released on every way out, after everything enqueued has finished
-        void *img = nullptr, *p = nullptr;
-        ~Scope() {
-            (void)hipStreamSynchronize(nullptr);
-            if (img) (void)hipFree(img);
-            if (p) (void)hipFree(p);
-        }
-    } sc;
-    const size_t rb = (size_t)cols * ch, pb = (size_t)n * pitch * sizeof(float);
-    hipStream_t s = nullptr;
-    MICV_HIP(hipMalloc(&sc.img, rb * rows));
-    MICV_HIP(hipMalloc(&sc.p, pb));
-    MICV_HIP(hipMemcpy2DAsync(sc.img, rb, img, stride, rb, rows, hipMemcpyHostToDevice, s));
-    MICV_HIP(hipMemcpyAsync(sc.p, p, pb, hipMemcpyHostToDevice, s));
-    MICV_TRY(launch_segments(ctx, static_cast<uint8_t *>(sc.img), rows, cols, ch, rb, static_cast<const float *>(sc.p), n, pitch, off2,
-                             color, s));
-    MICV_HIP(hipMemcpy2DAsync(img, stride, sc.img, rb, rb, rows, hipMemcpyDeviceToHost, s));
-    MICV_HIP(hipStreamSynchronize(s));
-    return MICV_OK;
+    HostCall h(ctx, fn);
+    const size_t rb = (size_t)cols * ch;
+    uint8_t *di = h.up<uint8_t>(img, stride, rb, rows);
+    float *dp = h.up<float>(p, (size_t)n * pitch * sizeof(float));
+    if (!h.ok()) return h.finish();
+    MICV_TRY(launch_segments(ctx, di, rows, cols, ch, rb, dp, n, pitch, off2, color, h.s));
+    h.down(img, stride, di, rb, rows);
+    return h.finish();
 }
 
 struct Picture {
@@ -178,7 +167,7 @@ int micv_draw_segments_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, int 
 int micv_draw_segments_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *segments, int n,
                             const double *color) {
     MICV_TRY(check_args("micv_draw_segments_host", ctx, img, rows, cols, channels, stride, segments, n, color));
-    return segments_host(ctx, img, rows, cols, channels, stride, segments, n, 4, 2, color);
+    return segments_host("micv_draw_segments_host", ctx, img, rows, cols, channels, stride, segments, n, 4, 2, color);
 }
 
 int micv_draw_epipolar_lines_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *endpoints,
@@ -190,7 +179,7 @@ int micv_draw_epipolar_lines_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols
 int micv_draw_epipolar_lines_host(micv_ctx *ctx, uint8_t *img, int rows, int cols, int channels, size_t stride, const float *endpoints,
                                   int n, const double *color) {
     MICV_TRY(check_args("micv_draw_epipolar_lines_host", ctx, img, rows, cols, channels, stride, endpoints, n, color));
-    return segments_host(ctx, img, rows, cols, channels, stride, endpoints, n, 6, 3, color);
+    return segments_host("micv_draw_epipolar_lines_host", ctx, img, rows, cols, channels, stride, endpoints, n, 6, 3, color);
 }
 
 int micv_ps3_epipolar_display_dev(micv_ctx *ctx, const float *F, const float *ptsA, const float *ptsB, int n, const uint8_t *imgA,
@@ -208,36 +197,19 @@ int micv_ps3_epipolar_display_host(micv_ctx *ctx, const float *F, const float *p
                                    size_t obstride, float *endpoints) {
     const Picture a{imgA, astride, rowsA, colsA, outA, oastride}, b{imgB, bstride, rowsB, colsB, outB, obstride};
     MICV_TRY(check_display("micv_ps3_epipolar_display_host", ctx, F, ptsA, ptsB, n, a, b, channels, flags, color));
-    MICV_HIP(hipSetDevice(ctx->device));
-    struct Scope {  // released on every way out, after everything enqueued has finished
-        void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Scope() {
-            (void)hipStreamSynchronize(nullptr);
-            for (void *q : p)
-                if (q) (void)hipFree(q);
-        }
-    } sc;
-    hipStream_t s = nullptr;
+    HostCall h(ctx, "micv_ps3_epipolar_display_host");
     const size_t rba = (size_t)colsA * channels, rbb = (size_t)colsB * channels, pb = (size_t)n * 2 * sizeof(float),
                  eb = (size_t)n * 12 * sizeof(float);
-    MICV_HIP(hipMalloc(&sc.p[0], rba * rowsA));
-    MICV_HIP(hipMalloc(&sc.p[1], rbb * rowsB));
-    MICV_HIP(hipMalloc(&sc.p[2], 2 * pb + 9 * sizeof(float)));  // ptsA, ptsB, F
-    if (endpoints) MICV_HIP(hipMalloc(&sc.p[3], eb));
-    uint8_t *da = static_cast<uint8_t *>(sc.p[0]), *db = static_cast<uint8_t *>(sc.p[1]);
-    float *dpa = static_cast<float *>(sc.p[2]), *dpb = dpa + 2 * (size_t)n, *dF = dpb + 2 * (size_t)n;
-    MICV_HIP(hipMemcpy2DAsync(da, rba, imgA, astride, rba, rowsA, hipMemcpyHostToDevice, s));
-    MICV_HIP(hipMemcpy2DAsync(db, rbb, imgB, bstride, rbb, rowsB, hipMemcpyHostToDevice, s));
-    MICV_HIP(hipMemcpyAsync(dpa, ptsA, pb, hipMemcpyHostToDevice, s));
-    MICV_HIP(hipMemcpyAsync(dpb, ptsB, pb, hipMemcpyHostToDevice, s));
-    MICV_HIP(hipMemcpyAsync(dF, F, 9 * sizeof(float), hipMemcpyHostToDevice, s));
+    uint8_t *da = h.up<uint8_t>(imgA, astride, rba, rowsA), *db = h.up<uint8_t>(imgB, bstride, rbb, rowsB);
+    float *dpa = h.up<float>(ptsA, pb), *dpb = h.up<float>(ptsB, pb), *dF = h.up<float>(F, 9 * sizeof(float));
+    float *de = endpoints ? h.alloc<float>(eb) : nullptr;
+    if (!h.ok()) return h.finish();
     const Picture ua{da, rba, rowsA, colsA, da, rba}, ub{db, rbb, rowsB, colsB, db, rbb};
-    MICV_TRY(enqueue_display(ctx, dF, dpa, dpb, n, ua, ub, channels, flags, color, static_cast<float *>(sc.p[3]), s));
-    MICV_HIP(hipMemcpy2DAsync(outA, oastride, da, rba, rba, rowsA, hipMemcpyDeviceToHost, s));
-    MICV_HIP(hipMemcpy2DAsync(outB, obstride, db, rbb, rbb, rowsB, hipMemcpyDeviceToHost, s));
-    if (endpoints) MICV_HIP(hipMemcpyAsync(endpoints, sc.p[3], eb, hipMemcpyDeviceToHost, s));
-    MICV_HIP(hipStreamSynchronize(s));
-    return MICV_OK;
+    MICV_TRY(enqueue_display(ctx, dF, dpa, dpb, n, ua, ub, channels, flags, color, de, h.s));
+    h.down(outA, oastride, da, rba, rowsA);
+    h.down(outB, obstride, db, rbb, rowsB);
+    if (endpoints) h.down(endpoints, de, eb);
+    return h.finish();
 }
 
 }  // extern "C"
