@@ -69,7 +69,8 @@ size_t micv_ctx_scratch_bytes(const micv_ctx *ctx);
 #define MICV_OPT_LK_SPLIT          15 /* fused LK, window 15: a level launch SPLIT in two (r05, lk_split.hip) -- a pre-pass (pyrUp + warp + Sobel once per pixel, Ix / Iy / It into padded planes in HBM) plus a streaming window-sum kernel that carries its row-pass rows from block to block: 0 = never (default: measured 28-42 % slower than the fused launch, HBM traffic 2.4-3x), 1 = every whole-frame launch of at least 64 x 64 with a doubling coarse flow, 2 = 1 with the base flow through u, v, 3 = the pre-pass leaves only the warped image and the second half is the fused kernel in its no-flow mode */
 #define MICV_OPT_LK_STRIP          16 /* fused LK, window 15: the INTERIOR tiles of a level launch as vertical strips that a workgroup streams down in blocks of 16 rows, carrying the last 14 row-pass rows of the five product fields and two warped rows from block to block (lk_strip.hpp) -- no vertical halo recomputation; the border tiles of the same launch stay tiles: 0 = off (default: 15 % fewer instructions, the same time -- DESIGN.md section 5), n > 0 = on with row segments of n blocks (16 = 256 rows); + 8192 = only for launches of 4096 tiles or more */
 #define MICV_OPT_STEREO_EXACT      17 /* disparitySSD on 8-bit-valued images (integers 0..255 in both f32 images, radius <= 7; serial:: semantics radius <= 5): 0 = the exact-sum kernels (stereo_exact.hip: integer dot products, sliding window sums, lanes = disparities), chosen on the device per call by a pre-pass that tests every pixel (default); -1 = always the float kernels that add every window in the contract's order.  Same disparities either way: all sums are integers below 2^24, exact in f32 in any order.  (disparityNCorr always takes the float kernels.) */
-#define MICV_OPT_COUNT            18
+#define MICV_OPT_STEREO_BATCH_MB   18 /* micv_disparity_ssd_u8_batch_dev: MiB of packed planes one launch may hold before the batch is processed in pieces: 0 = 64 (default), n = 1..4096 */
+#define MICV_OPT_COUNT            19
 int micv_ctx_set_option(micv_ctx *ctx, int option, int value);
 int micv_ctx_get_option(const micv_ctx *ctx, int option, int *value);
 
@@ -451,6 +452,44 @@ int micv_disparity_ssd_dev(micv_ctx *ctx, const float *left, const float *right,
 int micv_disparity_ssd_host(micv_ctx *ctx, const float *left, const float *right, int rows,
                             int cols, size_t stride, int window_rad, int min_disparity,
                             int max_disparity, int flags, int8_t *disp, size_t dstride);
+/* disparitySSD on 8-BIT images: what every stereo call of the reference starts from (main.cpp:87-88 loads 8-bit pictures
+ * and convertTo(CV_32FC1)s them only because cuda::disparitySSD asserts CV_32FC1, DisparitySSD.cu:149-150).
+ *
+ * Contract.  For every argument set micv_disparity_ssd_dev accepts (the same refusals, radius 0..31, all four flags), disp
+ * is byte-identical to micv_disparity_ssd_dev on the two images converted to f32.  Each image has its own row pitch in
+ * bytes (>= cols); pointers and pitches need NO alignment (a cv::Mat ROI of an 8-bit image starts at any byte).  Bytes of
+ * disp outside rows x cols (row padding) are not written.  No entry synchronises the host.
+ *
+ * Dispatch, decided on the host before anything is enqueued:
+ *   - radius 1..7, except SERIAL at radius 6 and 7 and COLS_2R at radius 1: the exact-sum kernels (stereo_exact.hip), from a
+ *     pre-pass that packs the bytes as they are -- no eligibility test, no write to the context's flag word, no float tiles
+ *     in the search launch; the call neither depends on nor disturbs the flag word of f32 calls on other streams.
+ *     (That removes one hazard, not the rule: calls that may overlap still need a context each, for the scratch arena.)  ROLLING is
+ *     served by the same kernels with the flag stripped (ROLLING | COLS_2R: the COLS_2R form; otherwise the full window):
+ *     the rolling column sums differ from the fresh ones only in the order of their roundings, and on bytes with a window
+ *     of at most 15 x 15 every sum is an integer below 2^24 -- exact in f32 in any order.
+ *   - everything else (radius 0 or > 7, SERIAL at radius 6 and 7, COLS_2R at radius 1, MICV_OPT_STEREO_EXACT = -1): the
+ *     pair is converted to f32 in the context's scratch by a small kernel and handed to micv_disparity_ssd_dev.
+ *
+ * Batch: `batch` pairs of one size, pair i at base + i * pair_stride (bytes; any value for the inputs, the disparity maps
+ * must not overlap), searched in ONE pre-pass and ONE search launch whose tiling sees the strips of all pairs -- a batch of
+ * small images fills the device where a single one cannot.  Element i is byte-identical to the single call on pair i;
+ * the gaps between the maps are not written.  Scratch: the packed planes of all pairs of a launch come from the context's
+ * arena, roughly 12 B per pixel and pair (16 B with MIN_SSD_5E6); a batch whose planes pass 64 MiB
+ * (MICV_OPT_STEREO_BATCH_MB) is processed in pieces.  A piece is as many pairs as keep its planes -- sized with the tiling
+ * the piece itself gets -- within the bound, one pair at least (a single pair may be larger than the bound) and at most 32768
+ * eight-row strips; the shorter last piece is tiled as the full ones, so no launch holds more than a full piece does. */
+int micv_disparity_ssd_u8_dev(micv_ctx *ctx, const uint8_t *left, size_t lstride, const uint8_t *right, size_t rstride,
+                              int rows, int cols, int window_rad, int min_disparity, int max_disparity, int flags,
+                              int8_t *disp, size_t dstride, micv_stream stream);
+/* Uploads 1 B per pixel and image (micv_disparity_ssd_host: 4). */
+int micv_disparity_ssd_u8_host(micv_ctx *ctx, const uint8_t *left, size_t lstride, const uint8_t *right, size_t rstride,
+                               int rows, int cols, int window_rad, int min_disparity, int max_disparity, int flags,
+                               int8_t *disp, size_t dstride);
+int micv_disparity_ssd_u8_batch_dev(micv_ctx *ctx, const uint8_t *left, size_t lpair_stride, size_t lstride,
+                                    const uint8_t *right, size_t rpair_stride, size_t rstride, int batch, int rows, int cols,
+                                    int window_rad, int min_disparity, int max_disparity, int flags, int8_t *disp,
+                                    size_t dpair_stride, size_t dstride, micv_stream stream);
 /* cuda::disparityNCorr, ps2_cpp/lib/DisparityNCorr.cu:177-251 (a13). */
 int micv_disparity_ncorr_dev(micv_ctx *ctx, const float *left, const float *right, int rows,
                              int cols, size_t stride, int window_rad, int min_disparity,

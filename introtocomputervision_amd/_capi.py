@@ -47,7 +47,7 @@ PS4_NO_GLYPHS = 1  # ps4 driver (mi_cv.h)
 (OPT_LK_STREAM_GROUPS, OPT_LK_FORCE_GENERIC, OPT_LK_NARROW_TILES, OPT_SOBEL_GENERIC, OPT_HARRIS_GENERIC,
  OPT_NMS_SCAN, OPT_STEREO_ROWS, OPT_LK_CHAIN, OPT_LK_SHORT_TILES, OPT_LK_STREAM, OPT_LK_TALL_TILES,
  OPT_COMPACT_3PASS, OPT_LK_DIRECT_LEVELS, OPT_LK_BUILD_OVERLAP, OPT_LK_SPLIT, OPT_LK_STRIP,
- OPT_STEREO_EXACT) = range(1, 18)
+ OPT_STEREO_EXACT, OPT_STEREO_BATCH_MB) = range(1, 19)
 
 
 MICV_COMM_ID_BYTES = 128  # mi_cv.h
@@ -144,6 +144,9 @@ SIGNATURES = {
     # ps2
     "micv_disparity_ssd_dev": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, vp, sz, vp]),
     "micv_disparity_ssd_host": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, vp, sz]),
+    "micv_disparity_ssd_u8_dev": (i32, [vp, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "micv_disparity_ssd_u8_host": (i32, [vp, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, vp, sz]),
+    "micv_disparity_ssd_u8_batch_dev": (i32, [vp, vp, sz, sz, vp, sz, sz, i32, i32, i32, i32, i32, i32, i32, vp, sz, sz, vp]),
     "micv_disparity_ncorr_dev": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, vp, sz, vp]),
     "micv_disparity_ncorr_host": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, vp, sz]),
     # ps1

@@ -521,6 +521,25 @@ int micv_disparity_ncorr_host(micv_ctx *ctx, const float *left, const float *rig
                        max_disparity, flags, disp, dstride);
 }
 
+// 1 B per pixel and image up, where the f32 entry sends 4
+int micv_disparity_ssd_u8_host(micv_ctx *ctx, const uint8_t *left, size_t lstride, const uint8_t *right, size_t rstride,
+                               int rows, int cols, int window_rad, int min_disparity, int max_disparity, int flags,
+                               int8_t *disp, size_t dstride) {
+    HostCall h(ctx, "micv_disparity_ssd_u8_host");
+    if (!h.ok()) return h.finish();
+    MICV_REQUIRE(left && right && disp && rows > 0 && cols > 0, "micv_disparity_ssd_u8_host: null argument or bad size");
+    MICV_REQUIRE(lstride >= (size_t)cols && rstride >= (size_t)cols && dstride >= (size_t)cols,
+                 "micv_disparity_ssd_u8_host: bad stride");
+    const size_t rb = (size_t)cols;
+    uint8_t *dl = h.up<uint8_t>(left, lstride, rb, rows), *dr = h.up<uint8_t>(right, rstride, rb, rows);
+    int8_t *dd = h.alloc<int8_t>(rb * rows);
+    if (!h.ok()) return h.finish();
+    MICV_TIMED(h, "disparitySSDKernel", micv_disparity_ssd_u8_dev(ctx, dl, rb, dr, rb, rows, cols, window_rad, min_disparity,
+                                                                  max_disparity, flags, dd, rb, h.s));
+    h.down(disp, dstride, dd, rb, rows);
+    return h.finish();
+}
+
 int micv_hough_lines_host(micv_ctx *ctx, const uint8_t *mask, int rows, int cols, size_t mstride,
                           unsigned rho_bin, unsigned theta_bin, int32_t *acc) {
     HostCall h(ctx, "micv_hough_lines_host");

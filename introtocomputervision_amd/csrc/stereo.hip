@@ -238,15 +238,15 @@ static int launch_stereo(hipStream_t s, const StereoArgs &a, int r, int force_rp
     return MICV_OK;
 }
 
-static int stereo_common(const char *fn, micv_ctx *ctx, const float *left, const float *right,
-                         int rows, int cols, size_t stride, int rad, int min_d, int max_d,
-                         int flags, int8_t *disp, size_t dstride, micv_stream stream, bool ncc) {
+// What every stereo entry refuses, f32 and u8 alike; `strides_ok` is the entry's own test of its row pitches.
+static int stereo_check(const char *fn, const void *ctx, const void *left, const void *right, int rows, int cols, int rad,
+                        int min_d, int max_d, int flags, const void *disp, bool strides_ok, bool ncc) {
     MICV_REQUIRE(ctx && left && right && disp, "%s: null argument", fn);
     MICV_REQUIRE(rows > 0 && cols > 0, "%s: bad size %dx%d", fn, rows, cols);
     MICV_REQUIRE(rad >= 0 && rad <= 31, "%s: window radius %d out of range 0..31", fn, rad);
     MICV_REQUIRE(min_d <= max_d && min_d >= -128 && max_d <= 127,
                  "%s: disparities [%d, %d] do not fit the int8 output (CV_8SC1)", fn, min_d, max_d);
-    MICV_REQUIRE(stride_ok(stride, cols, 4) && dstride >= (size_t)cols, "%s: bad stride", fn);
+    MICV_REQUIRE(strides_ok, "%s: bad stride", fn);
     MICV_REQUIRE((flags & ~15) == 0, "%s: unknown flags 0x%x", fn, flags);
     MICV_REQUIRE(!(ncc && (flags & MICV_STEREO_SERIAL)), "%s: SERIAL applies to SSD only", fn);
     MICV_REQUIRE(!((flags & MICV_STEREO_SERIAL) && (flags & MICV_STEREO_ROLLING)),
@@ -255,6 +255,14 @@ static int stereo_common(const char *fn, micv_ctx *ctx, const float *left, const
                  "%s: SERIAL takes neither COLS_2R nor MIN_SSD_5E6 (serial::disparitySSD has a (2r+1)^2 window and no "
                  "threshold)", fn);
     MICV_REQUIRE(!((flags & MICV_STEREO_COLS_2R) && rad == 0), "%s: COLS_2R needs radius >= 1", fn);
+    return MICV_OK;
+}
+
+static int stereo_common(const char *fn, micv_ctx *ctx, const float *left, const float *right,
+                         int rows, int cols, size_t stride, int rad, int min_d, int max_d,
+                         int flags, int8_t *disp, size_t dstride, micv_stream stream, bool ncc) {
+    MICV_TRY(stereo_check(fn, ctx, left, right, rows, cols, rad, min_d, max_d, flags, disp,
+                          stride_ok(stride, cols, 4) && dstride >= (size_t)cols, ncc));
     MICV_HIP(hipSetDevice(ctx->device));
     StereoArgs a;
     a.left = left; a.right = right; a.stride = (int)(stride / 4);
@@ -305,6 +313,80 @@ static int stereo_common(const char *fn, micv_ctx *ctx, const float *left, const
     return launch_stereo<ST_SSD>(s, a, rad, rpw);
 }
 
+// ---- disparitySSD on byte images (the u8 entries) -----------------------------------------------------------------------
+// Two byte images -> two dense f32 images, for the forms the exact-sum kernels do not cover.
+__global__ __launch_bounds__(256) void stereo_u8_to_f32_kernel(const uint8_t *left, size_t lstride, const uint8_t *right,
+                                                               size_t rstride, int rows, int cols, float *out) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= cols || y >= rows) return;
+    const uint8_t *src = blockIdx.z ? right + (size_t)y * rstride : left + (size_t)y * lstride;
+    out[((size_t)blockIdx.z * rows + y) * cols + x] = (float)src[x];
+}
+
+constexpr size_t kStereoU8BatchBytes = size_t(64) << 20;  // mi_cv.h: MICV_OPT_STEREO_BATCH_MB
+
+static int stereo_u8_common(const char *fn, micv_ctx *ctx, const uint8_t *left, size_t lpair, size_t lstride,
+                            const uint8_t *right, size_t rpair, size_t rstride, int batch, int rows, int cols, int rad,
+                            int min_d, int max_d, int flags, int8_t *disp, size_t dpair, size_t dstride, micv_stream stream) {
+    const size_t lim = (size_t)1 << 30;
+    MICV_TRY(stereo_check(fn, ctx, left, right, rows, cols, rad, min_d, max_d, flags, disp,
+                          rows > 0 && cols > 0 && lstride >= (size_t)cols && rstride >= (size_t)cols && dstride >= (size_t)cols &&
+                              lstride < lim && rstride < lim && dstride < lim, false));
+    MICV_REQUIRE(batch >= 1, "%s: batch %d", fn, batch);
+    MICV_REQUIRE(batch == 1 || dpair >= (size_t)(rows - 1) * dstride + (size_t)cols,
+                 "%s: the disparity maps of a batch overlap (pair stride %zu)", fn, dpair);
+    MICV_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // The dispatch, on the host: on bytes the rolling column sums ARE the fresh ones (integers below 2^24), so ROLLING
+    // goes where the call without it goes -- radius 1..7 to the exact-sum kernels.
+    const int xflags = (rad >= 1 && rad <= 7) ? flags & ~MICV_STEREO_ROLLING : flags;
+    if (ctx->opt[MICV_OPT_STEREO_EXACT] >= 0 && stereo_exact_covers(rad, xflags, false)) {
+        const int wcols = (xflags & MICV_STEREO_COLS_2R) ? 2 * rad : 2 * rad + 1, slots = ctx->wave_slots(3);
+        unsigned *flag;
+        MICV_TRY(ctx->stereo_flag_word(&flag));
+        // Pieces of a batch: as many pairs as keep a launch's planes within the bound (one pair at least), and no more strips
+        // than a grid has rows.  What a pair takes depends on the tiling, and the tiling on how many pairs it sees: the size
+        // is asked for the piece itself, and every piece -- the shorter last one too -- is tiled as the full piece is, so the
+        // one reservation holds each of them (stereo_exact_launch_u8 checks that against the bytes it is given).
+        const size_t bound = ctx->opt[MICV_OPT_STEREO_BATCH_MB] > 0 ? (size_t)ctx->opt[MICV_OPT_STEREO_BATCH_MB] << 20 : kStereoU8BatchBytes;
+        auto planes = [&](size_t pairs) {
+            return stereo_exact_scratch(rows, cols, rad, min_d, max_d, wcols, xflags, slots, (int)pairs, (int)pairs);
+        };
+        const size_t by_grid = 32768 / cdiv(rows, 8) < 1 ? 1 : 32768 / cdiv(rows, 8);
+        size_t piece = bound / planes(1) < 1 ? 1 : bound / planes(1);
+        if (piece > by_grid) piece = by_grid;
+        if (piece > (size_t)batch) piece = batch;
+        size_t bytes = planes(piece);
+        while (piece > 1 && bytes > bound) {  // (a piece's wider tiles can take a few per cent more per pair than a single pair's)
+            const size_t fit = piece * bound / bytes;
+            piece = fit < piece ? (fit < 1 ? 1 : fit) : piece - 1;
+            bytes = planes(piece);
+        }
+        void *scratch = nullptr;
+        MICV_TRY(ctx->reserve(bytes, &scratch));
+        for (int i = 0; i < batch; i += (int)piece) {
+            const int n = batch - i < (int)piece ? batch - i : (int)piece;
+            // (flag + 1: a word of the context's zero-filled block that no kernel writes)
+            MICV_TRY(stereo_exact_launch_u8(s, scratch, bytes, left + i * lpair, lpair, lstride, right + i * rpair, rpair, rstride, n,
+                                            (int)piece, rows, cols, rad, min_d, max_d, xflags, wcols, disp + i * dpair, dpair,
+                                            (int)dstride, flag + 1, slots));
+        }
+        return MICV_OK;
+    }
+    // Everything else: the pair as f32, in the context's chain block (the f32 entry carves the arena itself)
+    void *pool = nullptr;
+    MICV_TRY(ctx->reserve_chain(2 * (size_t)rows * cols * sizeof(float), &pool));
+    float *f = static_cast<float *>(pool);
+    for (int i = 0; i < batch; i++) {
+        stereo_u8_to_f32_kernel<<<dim3(cdiv(cols, 64), cdiv(rows, 4), 2), 256, 0, s>>>(left + i * lpair, lstride, right + i * rpair,
+                                                                                      rstride, rows, cols, f);
+        MICV_LAUNCH_CHECK();
+        MICV_TRY(stereo_common(fn, ctx, f, f + (size_t)rows * cols, rows, cols, (size_t)cols * 4, rad, min_d, max_d, flags,
+                               disp + i * dpair, dstride, stream, false));
+    }
+    return MICV_OK;
+}
+
 }  // namespace micv
 
 using namespace micv;
@@ -325,6 +407,21 @@ int micv_disparity_ncorr_dev(micv_ctx *ctx, const float *left, const float *righ
                              micv_stream stream) {
     return stereo_common("micv_disparity_ncorr", ctx, left, right, rows, cols, stride, window_rad,
                          min_disparity, max_disparity, flags, disp, dstride, stream, true);
+}
+
+int micv_disparity_ssd_u8_dev(micv_ctx *ctx, const uint8_t *left, size_t lstride, const uint8_t *right, size_t rstride,
+                              int rows, int cols, int window_rad, int min_disparity, int max_disparity, int flags,
+                              int8_t *disp, size_t dstride, micv_stream stream) {
+    return stereo_u8_common("micv_disparity_ssd_u8", ctx, left, 0, lstride, right, 0, rstride, 1, rows, cols, window_rad,
+                            min_disparity, max_disparity, flags, disp, 0, dstride, stream);
+}
+
+int micv_disparity_ssd_u8_batch_dev(micv_ctx *ctx, const uint8_t *left, size_t lpair_stride, size_t lstride,
+                                    const uint8_t *right, size_t rpair_stride, size_t rstride, int batch, int rows, int cols,
+                                    int window_rad, int min_disparity, int max_disparity, int flags, int8_t *disp,
+                                    size_t dpair_stride, size_t dstride, micv_stream stream) {
+    return stereo_u8_common("micv_disparity_ssd_u8_batch", ctx, left, lpair_stride, lstride, right, rpair_stride, rstride, batch,
+                            rows, cols, window_rad, min_disparity, max_disparity, flags, disp, dpair_stride, dstride, stream);
 }
 
 }  // extern "C"

@@ -34,6 +34,11 @@
 // (integer, 0..255) and writes the launch's epoch into the context's flag word on the first failure; the search launch
 // holds the exact-sum tiles and, behind them, the float kernel's tiles of the same call (stereo_float.hpp) -- whichever
 // the flag does not select leave at once.  MICV_OPT_STEREO_EXACT = -1 never takes this path.
+//
+// A caller who holds the 8-bit images themselves (micv_disparity_ssd_u8_*: stereo_exact_launch_u8) has nothing to guess:
+// the u8 pre-pass packs the bytes as they are and tests nothing, the search is pointed at a flag word nobody writes, and
+// its launch holds no float tiles.  The same two launches serve a BATCH of pairs of one size: the pre-pass lays the planes
+// out as batch x strips, and the search finds its pair from the strip index once per wave (StereoExactArgs: batch, spp).
 #include <utility>
 
 #include "kernels.hpp"
@@ -90,6 +95,61 @@ __device__ __forceinline__ void sx_colsums(const uint32_t (&l)[NG], const uint32
 // Energies: B(y, p) = window sum of right^2 at position p = x + d (window columns p - R .. p - R + wcols - 1, each
 // clamped on its own), p in [min_d, cols - 1 + max_d]; A(y, x) the same of left at x (only MIN_SSD_5E6 reads it).
 // One workgroup = 256 consecutive columns q of one strip, of which it owns the first 256 - (wcols - 1).
+//
+// The two halves every pre-pass shares (f32 and u8 images), around its __syncthreads.  First: thread u holds the packed
+// rows of column q of strip s (of the launch) -- it stores the plan record and the pack words it owns and leaves the
+// column sums of the squares for the windows that start in the workgroup's columns.
+template <int R, int NG>
+__device__ __forceinline__ void sx_prep_store(const StereoExactArgs &a, int s, int q, bool own, bool want_a,
+                                              const uint32_t (&lw)[SX_LW], const uint32_t (&rw)[NG],
+                                              uint32_t (&csB)[SX_Y][256 + 2 * R + 1], uint32_t (&csA)[SX_Y][256 + 2 * R + 1]) {
+    static_assert(NG == sx_groups(R), "packed words of a strip's window rows");
+    const int u = threadIdx.x;
+    if (own && q + R >= 0 && q + R < a.lcols) {
+        uint4 *lp = reinterpret_cast<uint4 *>(a.lplan + ((size_t)s * a.lcols + q + R) * SX_LW);
+        lp[0] = make_uint4(lw[0], lw[1], lw[2], lw[3]);
+        lp[1] = make_uint4(lw[4], lw[5], lw[6], lw[7]);
+    }
+    if (own && q >= 0 && q < a.cols) {
+#pragma unroll
+        for (int g = 0; g < NG; g++) a.rpack[((size_t)s * NG + g) * a.colsP + q] = rw[g];
+    }
+    uint32_t cs[SX_Y];
+    sx_colsums<R, NG>(rw, rw, cs, std::make_index_sequence<SX_Y>{});
+#pragma unroll
+    for (int j = 0; j < SX_Y; j++) csB[j][u] = cs[j];
+    if (want_a) {
+        uint32_t l5[NG];
+#pragma unroll
+        for (int g = 0; g < NG; g++) l5[g] = lw[g];
+        sx_colsums<R, NG>(l5, l5, cs, std::make_index_sequence<SX_Y>{});
+#pragma unroll
+        for (int j = 0; j < SX_Y; j++) csA[j][u] = cs[j];
+    }
+}
+// Second: the window energies of the strip's output rows ys .. ys + 7 (of its pair), rows yb + y of B and A.
+template <int R>
+__device__ __forceinline__ void sx_prep_energies(const StereoExactArgs &a, int ys, int yb, int q0, int nown, bool want_a,
+                                                 const uint32_t (&csB)[SX_Y][256 + 2 * R + 1],
+                                                 const uint32_t (&csA)[SX_Y][256 + 2 * R + 1]) {
+    const int p = q0 + (int)threadIdx.x + R;  // the window that starts at column q0 + t
+    const bool mine = (int)threadIdx.x < nown;
+    const bool b_ok = mine && p >= a.min_d && p - a.min_d < a.nB, a_ok = mine && want_a && p >= 0 && p < a.cols;
+    if (!b_ok && !a_ok) return;
+#pragma unroll
+    for (int j = 0; j < SX_Y; j++) {
+        const int y = ys + j;
+        if (y >= a.rows) break;
+        uint32_t eb = 0, ea = 0;
+        for (int i = 0; i < a.wcols; i++) eb += csB[j][threadIdx.x + i];
+        if (b_ok) a.B[(size_t)(yb + y) * a.nB + (p - a.min_d)] = (int32_t)eb;
+        if (a_ok) {
+            for (int i = 0; i < a.wcols; i++) ea += csA[j][threadIdx.x + i];
+            a.A[(size_t)(yb + y) * a.cols + p] = (int32_t)ea;
+        }
+    }
+}
+
 template <int R>
 __global__ __launch_bounds__(256) void stereo_prep_kernel(StereoExactArgs a) {
     constexpr int NR = SX_Y + 2 * R, NG = sx_groups(R), WMAX = 2 * R + 1;
@@ -127,46 +187,68 @@ __global__ __launch_bounds__(256) void stereo_prep_kernel(StereoExactArgs a) {
             lw[k >> 2] |= (ul & 255u) << (8 * (k & 3));
             rw[k >> 2] |= (ur & 255u) << (8 * (k & 3));
         }
-        if (own && q + R >= 0 && q + R < a.lcols) {
-            uint4 *lp = reinterpret_cast<uint4 *>(a.lplan + ((size_t)s * a.lcols + q + R) * SX_LW);
-            lp[0] = make_uint4(lw[0], lw[1], lw[2], lw[3]);
-            lp[1] = make_uint4(lw[4], lw[5], lw[6], lw[7]);
-        }
-        if (own && q >= 0 && q < a.cols) {
-#pragma unroll
-            for (int g = 0; g < NG; g++) a.rpack[((size_t)s * NG + g) * a.colsP + q] = rw[g];
-        }
-        uint32_t cs[SX_Y];
-        sx_colsums<R, NG>(rw, rw, cs, std::make_index_sequence<SX_Y>{});
-#pragma unroll
-        for (int j = 0; j < SX_Y; j++) csB[j][u] = cs[j];
-        if (want_a) {
-            uint32_t l5[NG];
-#pragma unroll
-            for (int g = 0; g < NG; g++) l5[g] = lw[g];
-            sx_colsums<R, NG>(l5, l5, cs, std::make_index_sequence<SX_Y>{});
-#pragma unroll
-            for (int j = 0; j < SX_Y; j++) csA[j][u] = cs[j];
-        }
+        sx_prep_store<R>(a, s, q, own, want_a, lw, rw, csB, csA);
     }
     if (!ok) *a.flag = a.epoch;  // every failing thread stores the same word
     __syncthreads();
-    const int p = q0 + (int)threadIdx.x + R;  // the window that starts at column q0 + t
-    const bool mine = (int)threadIdx.x < nown;
-    const bool b_ok = mine && p >= a.min_d && p - a.min_d < a.nB, a_ok = mine && want_a && p >= 0 && p < a.cols;
-    if (!b_ok && !a_ok) return;
+    sx_prep_energies<R>(a, s * SX_Y, 0, q0, nown, want_a, csB, csA);
+}
+
+// The same pre-pass straight from BYTE images, for every pair of a batch in one launch (the u8 entry points): blockIdx.y
+// is the strip of the launch = strip ys / 8 of pair `pair`.  Nothing to test and no flag to store: bytes are 0..255.
+// The source is 1 B per pixel at ANY address and pitch, so a row is not fetched pixel by pixel: the workgroup's 256
+// columns (clamped: c_lo .. c_hi) of a row are the aligned dwords first .. last that hold them -- at most 65, none of
+// which lies wholly outside the row, so none leaves the pages the row is in -- loaded as dwords by whichever threads come to them and
+// laid down in LDS; a thread then picks its column's byte of every row from there, at the row's own
+// misalignment (the pitch may be odd: every row and each image has its own).
+template <int R>
+__global__ __launch_bounds__(256) void stereo_prep_u8_kernel(StereoExactArgs a) {
+    constexpr int NR = SX_Y + 2 * R, NG = sx_groups(R), WMAX = 2 * R + 1;
+    constexpr int DW = 65;                              // dwords that hold 256 bytes at any misalignment
+    constexpr int NIT = (2 * NR * DW + 255) / 256;
+    __shared__ uint32_t csB[SX_Y][256 + WMAX], csA[SX_Y][256 + WMAX];
+    __shared__ uint32_t raw[2 * NR][DW];                // [image * NR + row]
+    const int nown = 256 - (a.wcols - 1);
+    const int s = blockIdx.y, pair = s / a.spp, ys = (s - pair * a.spp) * SX_Y;
+    const int q0 = a.qlo + blockIdx.x * nown;
+    const bool want_a = a.min_ssd_5e6 != 0;
+    const int c_lo = clampi(q0, 0, a.cols - 1), c_hi = clampi(q0 + 255, 0, a.cols - 1);
+    const uint8_t *const limg = a.left8 + (size_t)pair * a.lpair8, *const rimg = a.right8 + (size_t)pair * a.rpair8;
+    auto row_at = [&](int im, int k) {  // address of column c_lo of window row k of the strip
+        const int yy = clampi(ys - R + k, 0, a.rows - 1);
+        return reinterpret_cast<uintptr_t>(im ? rimg + (size_t)yy * a.rstride8 : limg + (size_t)yy * a.lstride8) + (uintptr_t)c_lo;
+    };
+    // the 2 NR x DW dwords spread over the 256 threads, whichever row they fall in (a wave per row, with scalar row
+    // addresses, measured slower: 19.9 against 18.2 us at 1080p, profiles/stereo_u8)
 #pragma unroll
-    for (int j = 0; j < SX_Y; j++) {
-        const int y = s * SX_Y + j;
-        if (y >= a.rows) break;
-        uint32_t eb = 0, ea = 0;
-        for (int i = 0; i < a.wcols; i++) eb += csB[j][threadIdx.x + i];
-        if (b_ok) a.B[(size_t)y * a.nB + (p - a.min_d)] = (int32_t)eb;
-        if (a_ok) {
-            for (int i = 0; i < a.wcols; i++) ea += csA[j][threadIdx.x + i];
-            a.A[(size_t)y * a.cols + p] = (int32_t)ea;
+    for (int it = 0; it < NIT; it++) {
+        const int e = it * 256 + (int)threadIdx.x, rk = e / DW, t = e - rk * DW;
+        if (rk < 2 * NR) {
+            const uintptr_t p = row_at(rk >= NR, rk >= NR ? rk - NR : rk);
+            const uintptr_t first = p & ~(uintptr_t)3, last = (p + (uintptr_t)(c_hi - c_lo)) & ~(uintptr_t)3;
+            if (first + 4 * (uintptr_t)t <= last) raw[rk][t] = *reinterpret_cast<const uint32_t *>(first + 4 * (uintptr_t)t);
         }
     }
+    __syncthreads();
+    {
+        const int u = threadIdx.x;
+        const int q = q0 + u, off = clampi(q, 0, a.cols - 1) - c_lo;
+        uint32_t lw[SX_LW], rw[NG];
+#pragma unroll
+        for (int g = 0; g < SX_LW; g++) lw[g] = 0;
+#pragma unroll
+        for (int g = 0; g < NG; g++) rw[g] = 0;
+#pragma unroll
+        for (int k = 0; k < NR; k++) {
+            const uint32_t ul = reinterpret_cast<const uint8_t *>(raw[k])[(row_at(0, k) & 3) + off];
+            const uint32_t ur = reinterpret_cast<const uint8_t *>(raw[NR + k])[(row_at(1, k) & 3) + off];
+            lw[k >> 2] |= ul << (8 * (k & 3));
+            rw[k >> 2] |= ur << (8 * (k & 3));
+        }
+        sx_prep_store<R>(a, s, q, u < nown, want_a, lw, rw, csB, csA);
+    }
+    __syncthreads();
+    sx_prep_energies<R>(a, ys, pair * a.rows, q0, nown, want_a, csB, csA);
 }
 
 // ---- the search ------------------------------------------------------------------------------------------------
@@ -252,7 +334,11 @@ void stereo_exact_kernel(StereoExactArgs a, StereoArgs f) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int tile = blockIdx.x * 4 + wave;
     if (tile >= a.ntiles) return;  // whole wave; waves never synchronise with each other
-    const int s = tile / a.nxs, ys = s * SX_Y, x0 = (tile - s * a.nxs) * a.X;
+    const int s = tile / a.nxs, x0 = (tile - s * a.nxs) * a.X;
+    // strip s of the launch is strip s - pair * spp of pair `pair` (a single pair: pair = 0, and nothing below moves)
+    const int pair = s / a.spp, ys = (s - pair * a.spp) * SX_Y;
+    const int yb = pair * a.rows;                               // the pair's first row of A and B
+    int8_t *const dmap = a.disp + (size_t)pair * a.dpair;   // its disparity map
     const int nchunks = (a.max_d - a.min_d) / 64 + 1;
     const SxLds lay = sx_lds_layout(NG, a.X, WC, nchunks);
     uint32_t *Rs = sx_lds + wave * lay.words();
@@ -286,7 +372,7 @@ void stereo_exact_kernel(StereoExactArgs a, StereoArgs f) {
 #pragma unroll
                 for (int j = 0; j < SX_Y; j++) {
                     const int y = ys + j < a.rows ? ys + j : a.rows - 1;
-                    t[q][j] = a.B[(size_t)y * a.nB + pi];
+                    t[q][j] = a.B[(size_t)(yb + y) * a.nB + pi];
                 }
             }
 #pragma unroll
@@ -425,10 +511,10 @@ void stereo_exact_kernel(StereoExactArgs a, StereoArgs f) {
                         if (SERIAL) {
                             if (score < -12000000) d = 0;  // no position inside the padded image: DisparitySSD.cpp:37
                         } else if (a.min_ssd_5e6) {
-                            const int ssd = a.A[(size_t)y * a.cols + x] - score;
+                            const int ssd = a.A[(size_t)(yb + y) * a.cols + x] - score;
                             if (!(ssd < 5000000)) d = -1;  // DisparitySSD.cu:16,177
                         }
-                        a.disp[(size_t)y * a.dstride + x] = (int8_t)d;
+                        dmap[(size_t)y * a.dstride + x] = (int8_t)d;
                     }
                 }
             }
@@ -443,13 +529,14 @@ void stereo_exact_kernel(StereoExactArgs a, StereoArgs f) {
 
 template <int R, int WC, int MODE, int RPW>
 static int launch_search(hipStream_t s, StereoExactArgs a, const StereoArgs &f) {
+    const bool with_float = a.left8 == nullptr;  // byte images have no float tiles: nothing to fall back from
     const int nchunks = (a.max_d - a.min_d) / 64 + 1;
     const size_t lds_exact = 4 * (size_t)sx_lds_layout(sx_groups(R), a.X, WC, nchunks).words() * sizeof(uint32_t);
-    const size_t lds_float = 4 * (size_t)(RPW + 2 * R) * (64 + ST_DCH_DEFAULT) * sizeof(float);
+    const size_t lds_float = with_float ? 4 * (size_t)(RPW + 2 * R) * (64 + ST_DCH_DEFAULT) * sizeof(float) : 0;
     const size_t lds = lds_exact > lds_float ? lds_exact : lds_float;
     a.nblk_exact = cdiv(a.ntiles, 4);
     a.fgx = cdiv(a.cols, 64 - 2 * R);
-    const int nblk_float = a.fgx * (int)cdiv(a.rows, 4 * RPW);
+    const int nblk_float = with_float ? a.fgx * (int)cdiv(a.rows, 4 * RPW) : 0;
     auto k = stereo_exact_kernel<R, WC, MODE, RPW>;
     static size_t attr_set[16] = {0};  // per device: the launch may need more than 64 KB of dynamic LDS
     int dev = 0;
@@ -466,8 +553,9 @@ static int launch_search(hipStream_t s, StereoExactArgs a, const StereoArgs &f) 
 // Only the forms stereo_exact_covers() admits are instantiated: serial:: with the full window and R <= 5, COLS_2R for R >= 2.
 template <int R, int RPW>
 static int launch_r(hipStream_t s, const StereoExactArgs &a, const StereoArgs &f, bool serial) {
-    const int nstrips = cdiv(a.rows, SX_Y);
-    stereo_prep_kernel<R><<<dim3(cdiv(a.qhi - a.qlo, 256 - (a.wcols - 1)), nstrips), 256, 0, s>>>(a);
+    const dim3 grid(cdiv(a.qhi - a.qlo, 256 - (a.wcols - 1)), a.batch * a.spp);
+    if (a.left8) stereo_prep_u8_kernel<R><<<grid, 256, 0, s>>>(a);
+    else stereo_prep_kernel<R><<<grid, 256, 0, s>>>(a);
     MICV_LAUNCH_CHECK();
     if constexpr (R <= 5) {
         if (serial) return launch_search<R, 2 * R + 1, SX_SERIAL, RPW>(s, a, f);
@@ -487,7 +575,8 @@ bool stereo_exact_covers(int rad, int flags, bool ncc) {
     // (0.88 / 0.60 ms against 0.316; profiles/r06/stereo_exact.md)
     if (ncc) return false;
     // ROLLING is a compatibility mode with a kernel of its own (on 8-bit-valued images it equals the fresh sums, so nothing is
-    // lost in results; its float fallback is not the tile the exact-sum launch carries)
+    // lost in results; its float fallback is not the tile the exact-sum launch carries -- the u8 entries, which have no
+    // fallback, strip the flag before they ask)
     if (flags & MICV_STEREO_ROLLING) return false;
     if (rad < 1 || rad > 7) return false;                       // (2r+1)^2 * 255^2 < 2^24
     if ((flags & MICV_STEREO_SERIAL) && rad > 5) return false;  // the invalid-position keys need a spare bit
@@ -498,9 +587,11 @@ bool stereo_exact_covers(int rad, int flags, bool ncc) {
 }
 
 // Output columns per wave: a wave's work is X + wcols - 1 columns (+ staging); the launch takes ceil(waves / slots)
-// rounds of the chip's resident waves.  Picks the strip count with the least (rounds x columns).
-static void sx_tiling(int rows, int cols, int rad, int wcols, int nchunks, int wave_slots3, int *X_out, int *nxs_out) {
-    const int nstrips = cdiv(rows, SX_Y), XMAX = 128;
+// rounds of the chip's resident waves.  Picks the strip count with the least (rounds x columns).  A batch is one launch:
+// the rounds are those of all its pairs' strips, so a batch of small images takes the wide tiles a single one cannot fill
+// the chip with.
+static void sx_tiling(int batch, int rows, int cols, int rad, int wcols, int nchunks, int wave_slots3, int *X_out, int *nxs_out) {
+    const int nstrips = batch * (int)cdiv(rows, SX_Y), XMAX = 128;
     long best_cost = -1;
     int bx = XMAX, bn = cdiv(cols, XMAX);
     for (int nxs = cdiv(cols, XMAX); nxs <= 6 * (int)cdiv(cols, XMAX) && nxs <= cols; nxs++) {
@@ -523,10 +614,13 @@ static void sx_tiling(int rows, int cols, int rad, int wcols, int nchunks, int w
     *nxs_out = bn;
 }
 
-static void sx_geometry(StereoExactArgs &a, int rad, int wave_slots3) {
+// `tile_batch`: the pairs whose strips the tiling prices (a.batch, or the full piece of the batch this launch is a piece of:
+// every piece then has the same X, nxs and lcols, so a pair takes the same bytes in each)
+static void sx_geometry(StereoExactArgs &a, int rad, int wave_slots3, int tile_batch) {
     const int nchunks = (a.max_d - a.min_d) / 64 + 1;
-    sx_tiling(a.rows, a.cols, rad, a.wcols, nchunks, wave_slots3, &a.X, &a.nxs);
-    a.ntiles = (int)cdiv(a.rows, SX_Y) * a.nxs;
+    a.spp = cdiv(a.rows, SX_Y);
+    sx_tiling(tile_batch, a.rows, a.cols, rad, a.wcols, nchunks, wave_slots3, &a.X, &a.nxs);
+    a.ntiles = a.batch * a.spp * a.nxs;
     a.colsP = (a.cols + 63) & ~63;
     a.nB = a.cols + (a.max_d - a.min_d);
     a.lcols = a.nxs * a.X + 4 * rad + 8 + 2 * (2 * rad + 1);  // window columns of every strip incl. the loop's overrun
@@ -537,33 +631,39 @@ static void sx_geometry(StereoExactArgs &a, int rad, int wave_slots3) {
     if (a.qhi < a.cols) a.qhi = a.cols;
 }
 
-size_t stereo_exact_scratch(int rows, int cols, int rad, int min_d, int max_d, int wcols, int flags, int wave_slots3) {
-    StereoExactArgs a;
-    a.rows = rows; a.cols = cols; a.min_d = min_d; a.max_d = max_d; a.wcols = wcols;
-    sx_geometry(a, rad, wave_slots3);
-    const int nstrips = cdiv(rows, SX_Y);
-    return Carver::need((size_t)nstrips * a.lcols * SX_LW, 4) + Carver::need((size_t)nstrips * sx_groups(rad) * a.colsP, 4) +
-           ((flags & MICV_STEREO_MIN_SSD_5E6) ? Carver::need((size_t)rows * cols, 4) : 0) + Carver::need((size_t)rows * a.nB, 4);
+// The planes of a launch, carved in this order: batch x (plan, pack, A under MIN_SSD_5E6, B).  Returns their bytes; with
+// scratch = null that is all it does.
+static size_t sx_carve(StereoExactArgs &a, int rad, int flags, void *scratch) {
+    const size_t nstrips = (size_t)a.batch * a.spp, nrows = (size_t)a.batch * a.rows;
+    size_t off = 0;
+    auto take = [&](size_t words) {
+        void *p = scratch ? static_cast<char *>(scratch) + off : nullptr;
+        off += Carver::need(words, 4);
+        return p;
+    };
+    a.lplan = static_cast<uint32_t *>(take(nstrips * a.lcols * SX_LW));
+    a.rpack = static_cast<uint32_t *>(take(nstrips * sx_groups(rad) * a.colsP));
+    a.A = (flags & MICV_STEREO_MIN_SSD_5E6) ? static_cast<int32_t *>(take(nrows * a.cols)) : nullptr;  // only the 5e6 threshold reads it
+    a.B = static_cast<int32_t *>(take(nrows * a.nB));
+    return off;
 }
 
-int stereo_exact_launch(hipStream_t s, void *scratch, const float *left, const float *right, int rows, int cols,
-                        int stride, int rad, int min_d, int max_d, int flags, int wcols, int8_t *disp, int dstride,
-                        unsigned *flag, unsigned epoch, int wave_slots3, const StereoArgs &f, bool rows10) {
-    // decided before anything is enqueued: launch_r instantiates exactly the forms this admits
-    if (!stereo_exact_covers(rad, flags, false)) return MICV_EUNSUPPORTED;
-    StereoExactArgs a;
-    const int nstrips = cdiv(rows, SX_Y);
-    a.left = left; a.right = right; a.stride = stride; a.rows = rows; a.cols = cols;
-    a.min_d = min_d; a.max_d = max_d; a.wcols = wcols;
-    sx_geometry(a, rad, wave_slots3);
-    Carver cv(scratch);
-    a.lplan = cv.take<uint32_t>((size_t)nstrips * a.lcols * SX_LW);
-    a.rpack = cv.take<uint32_t>((size_t)nstrips * sx_groups(rad) * a.colsP);
-    a.A = (flags & MICV_STEREO_MIN_SSD_5E6) ? cv.take<int32_t>((size_t)rows * cols) : nullptr;  // only the 5e6 threshold reads it
-    a.B = cv.take<int32_t>((size_t)rows * a.nB);
-    a.flag = flag; a.epoch = epoch;
-    a.disp = disp; a.dstride = dstride;
+static void sx_setup(StereoExactArgs &a, int batch, int tile_batch, int rows, int cols, int rad, int min_d, int max_d, int flags,
+                     int wcols, int wave_slots3) {
+    a = StereoExactArgs{};
+    a.batch = batch; a.rows = rows; a.cols = cols; a.min_d = min_d; a.max_d = max_d; a.wcols = wcols;
     a.min_ssd_5e6 = (flags & MICV_STEREO_MIN_SSD_5E6) ? 1 : 0;
+    sx_geometry(a, rad, wave_slots3, tile_batch > batch ? tile_batch : batch);
+}
+
+size_t stereo_exact_scratch(int rows, int cols, int rad, int min_d, int max_d, int wcols, int flags, int wave_slots3, int batch,
+                            int tile_batch) {
+    StereoExactArgs a;
+    sx_setup(a, batch, tile_batch, rows, cols, rad, min_d, max_d, flags, wcols, wave_slots3);
+    return sx_carve(a, rad, flags, nullptr);
+}
+
+static int sx_launch(hipStream_t s, const StereoExactArgs &a, const StereoArgs &f, int rad, int flags, bool rows10) {
     const bool serial = flags & MICV_STEREO_SERIAL;
 #define MICV_SX_CASE(RR) \
     case RR: return rows10 ? launch_r<RR, 10>(s, a, f, serial) : launch_r<RR, 8>(s, a, f, serial);
@@ -572,6 +672,42 @@ int stereo_exact_launch(hipStream_t s, void *scratch, const float *left, const f
     }
 #undef MICV_SX_CASE
     return MICV_EUNSUPPORTED;
+}
+
+int stereo_exact_launch(hipStream_t s, void *scratch, const float *left, const float *right, int rows, int cols,
+                        int stride, int rad, int min_d, int max_d, int flags, int wcols, int8_t *disp, int dstride,
+                        unsigned *flag, unsigned epoch, int wave_slots3, const StereoArgs &f, bool rows10) {
+    // decided before anything is enqueued: launch_r instantiates exactly the forms this admits
+    if (!stereo_exact_covers(rad, flags, false)) return MICV_EUNSUPPORTED;
+    StereoExactArgs a;
+    sx_setup(a, 1, 1, rows, cols, rad, min_d, max_d, flags, wcols, wave_slots3);
+    sx_carve(a, rad, flags, scratch);
+    a.left = left; a.right = right; a.stride = stride;
+    a.flag = flag; a.epoch = epoch;
+    a.disp = disp; a.dstride = dstride;
+    return sx_launch(s, a, f, rad, flags, rows10);
+}
+
+int stereo_exact_launch_u8(hipStream_t s, void *scratch, size_t scratch_bytes, const uint8_t *left, size_t lpair, size_t lstride,
+                           const uint8_t *right, size_t rpair, size_t rstride, int batch, int tile_batch, int rows, int cols,
+                           int rad, int min_d, int max_d, int flags, int wcols, int8_t *disp, size_t dpair, int dstride,
+                           unsigned *never, int wave_slots3) {
+    if (!stereo_exact_covers(rad, flags, false)) return MICV_EUNSUPPORTED;
+    StereoExactArgs a;
+    sx_setup(a, batch, tile_batch, rows, cols, rad, min_d, max_d, flags, wcols, wave_slots3);
+    // the planes are laid out HERE: whatever the caller sized its block from, a launch that would write past it does not start
+    const size_t need = sx_carve(a, rad, flags, scratch);
+    if (need > scratch_bytes) {
+        set_error("stereo_exact_launch_u8: %zu B of planes for %d pairs in a block of %zu B", need, batch, scratch_bytes);
+        return MICV_EINVAL;
+    }
+    a.left8 = left; a.right8 = right; a.lpair8 = lpair; a.rpair8 = rpair; a.lstride8 = lstride; a.rstride8 = rstride;
+    // the word holds 0 and nobody writes it: with epoch 1 the search never sees "float images", whatever the f32 calls of
+    // other streams do to the context's flag word meanwhile
+    a.flag = never; a.epoch = 1;
+    a.disp = disp; a.dstride = dstride; a.dpair = dpair;
+    // (the search's float tiles are not launched: the rows-per-wave argument only names the instantiation)
+    return sx_launch(s, a, StereoArgs{}, rad, flags, false);
 }
 
 }  // namespace micv

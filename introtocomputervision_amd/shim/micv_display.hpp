@@ -85,6 +85,17 @@ inline void check_pair(const Mat &left, const Mat &right, const char *what) {
 }
 inline void pair(bool ncc, const Mat &left, const Mat &right, const bool useGpuDisparity, const DisparityConfig &config,
                  Mat &leftDisparity, Mat &rightDisparity) {
+    if (left.type() == micv_shim::U8 || right.type() == micv_shim::U8) {
+        // 8-bit Mats (SSD only; micv_shim::disparity refuses NCC with a message): the two searches of main.cpp:21-48 as
+        // two u8 calls -- the left image as reference over [-range, 0], the right one over [0, range]
+        const int range = (int)config._disparityRange, flags = stereo_flags(ncc, useGpuDisparity);
+        Mat l, r;
+        micv_shim::disparity(ncc, left, right, config._windowRadius, -range, 0, flags, l);
+        micv_shim::disparity(ncc, right, left, config._windowRadius, 0, range, flags, r);
+        leftDisparity = l;
+        rightDisparity = r;
+        return;
+    }
     check_pair(left, right, "disparity pair: CV_32FC1 images of equal size expected");
     Mat l, r;
     l.create(left.rows, left.cols, micv_shim::S8);

@@ -578,6 +578,18 @@ private:
 namespace micv_shim {
 inline void disparity(bool ncc, const Mat &left, const Mat &right, const size_t windowRad,
                       const int minDisparity, const int maxDisparity, int flags, Mat &disparity) {
+    // The 8-bit images main.cpp loads, without its convertTo(CV_32FC1) (main.cpp:87-88): SSD takes them as they are, each
+    // with its own step (an ROI starts at any byte); the disparities are those of the converted pair.
+    if (left.type() == U8 || right.type() == U8) {
+        require(!ncc, "disparityNCorr: CV_32FC1 images expected (8-bit pairs are taken by disparitySSD only)");
+        require(left.type() == U8 && right.type() == U8 && left.rows == right.rows && left.cols == right.cols,
+                "disparitySSD: CV_8UC1 pair of equal size expected");
+        disparity.create(left.rows, left.cols, S8);
+        check(micv_disparity_ssd_u8_host(context(), left.ptr<uint8_t>(), left.step, right.ptr<uint8_t>(), right.step, left.rows,
+                                         left.cols, static_cast<int>(windowRad), minDisparity, maxDisparity, flags,
+                                         disparity.ptr<int8_t>(), disparity.step));
+        return;
+    }
     require(left.type() == F32 && right.type() == F32 && left.rows == right.rows &&
                 left.cols == right.cols && left.step == right.step,
             "disparity: CV_32FC1 pair of equal size expected");  // DisparitySSD.cpp:15
