@@ -1054,6 +1054,53 @@ int micv_mhi_history_seq_host(micv_ctx *ctx, const uint8_t *frames, int nframes,
                               int rows, int cols, double thresh, int blur_w, int blur_h, double blur_sigma, int tau,
                               const int *save, int nsave, uint8_t *out, size_t out_pitch, size_t out_stride);
 
+/* mhi::frameDifference on the frames mhiHelper hands it (Solution.cpp:16-101: `vid >> frame`, CV_8UC3): `channels`
+ * is 1, 3 or 4, samples interleaved, `stride` in bytes and >= cols * channels, any base address.  diff is rows x cols
+ * u8 as above.  Contract for 3 and 4 channels (MotionHistory.cpp:50-73; the arithmetic of cv::cuda is restated, not
+ * pinned to a build of it):
+ *   blur      every channel as a plane of its own by the single-channel contract: gaussian taps, row pass then column
+ *             pass, acc = fmaf(x, k, acc) from +0, BORDER_REFLECT_101, round half to even, saturate to u8.  The 4th
+ *             channel is not blurred: nothing reads it.
+ *   subtract  per channel, d_c = max(b2_c - b1_c, 0) (cv::cuda::subtract on CV_8UC3).
+ *   grey      g = (d_0 * 4899 + d_1 * 9617 + d_2 * 1868 + 8192) >> 14, the 8-bit rule of micv_to_gray_f32: channel 0
+ *             carries the 0.299 weight AS WRITTEN (cvtColor(COLOR_RGB2GRAY) on the capture's BGR data).  The weights
+ *             sum to 16384, so g <= 255.  Channel 3 is ignored.
+ *   then      AbsThreshold on g and the 7x7 elliptical open, as above.
+ * channels == 1 gives the bytes of micv_mhi_frame_difference_dev.  The grey step follows the subtraction: a channel
+ * whose difference saturates at 0 does not pull the others down, which grey-then-subtract would. */
+int micv_mhi_frame_difference_c_dev(micv_ctx *ctx, const uint8_t *f1, const uint8_t *f2, int rows, int cols, int channels,
+                                    size_t stride, double thresh, int blur_w, int blur_h, double blur_sigma, uint8_t *diff,
+                                    size_t dstride, micv_stream stream);
+int micv_mhi_frame_difference_c_host(micv_ctx *ctx, const uint8_t *f1, const uint8_t *f2, int rows, int cols, int channels,
+                                     size_t stride, double thresh, int blur_w, int blur_h, double blur_sigma, uint8_t *diff,
+                                     size_t dstride);
+/* micv_mhi_history_seq_* on frames of 1, 3 or 4 channels, with mhiHelper's second list: save_diff[i] = j stores the
+ * {0,1} mask of update j into diff_out + i * diff_pitch (rows of diff_stride bytes), as save[i] = j stores the history
+ * (saveDiffFrames and saveMHIFrames).  Either list may be empty (count 0, pointers NULL) but not both; the loop runs to
+ * the larger of the two maxima.  One channel and no diff saves give the bytes of micv_mhi_history_seq_dev. */
+int micv_mhi_history_seq_c_dev(micv_ctx *ctx, const uint8_t *frames, int nframes, size_t frame_pitch, size_t stride, int rows,
+                               int cols, int channels, double thresh, int blur_w, int blur_h, double blur_sigma, int tau,
+                               const int *save, int nsave, uint8_t *out, size_t out_pitch, size_t out_stride,
+                               const int *save_diff, int nsave_diff, uint8_t *diff_out, size_t diff_pitch, size_t diff_stride,
+                               micv_stream stream);
+int micv_mhi_history_seq_c_host(micv_ctx *ctx, const uint8_t *frames, int nframes, size_t frame_pitch, size_t stride, int rows,
+                                int cols, int channels, double thresh, int blur_w, int blur_h, double blur_sigma, int tau,
+                                const int *save, int nsave, uint8_t *out, size_t out_pitch, size_t out_stride,
+                                const int *save_diff, int nsave_diff, uint8_t *diff_out, size_t diff_pitch, size_t diff_stride);
+/* getAllMHIs' loop (Solution.cpp:113-146) over nvideos videos in one call.  Shared: rows, cols, channels, stride,
+ * frame_pitch and the blur.  Per video v (host arrays of nvideos entries): frames[v], a DEVICE pointer to its frame 0;
+ * nframes[v]; thresh[v]; tau[v]; save[v] in 1..nframes[v]-1.  out + v * out_pitch (rows of out_stride bytes) receives
+ * the history after update save[v], byte-equal to micv_mhi_history_seq_c_dev with that one save number.  Step j is two
+ * launches over every video with save[v] >= j (the update is fused into the open's byte write, and the output plane is
+ * the history); a video past its save number is skipped and its output not touched again.  Stream-ordered, no host
+ * synchronisation; the host arrays are not read after the call returns (the table travels by value with the launches).
+ * Batches above 32 videos, or whose mask words exceed 64 MiB, run in pieces.  Bad arguments return MICV_EINVAL before
+ * anything is enqueued. */
+int micv_mhi_history_batch_dev(micv_ctx *ctx, const uint8_t *const *frames, const int *nframes, size_t frame_pitch, size_t stride,
+                               int nvideos, int rows, int cols, int channels, const double *thresh, const int *tau, const int *save,
+                               int blur_w, int blur_h, double blur_sigma, uint8_t *out, size_t out_pitch, size_t out_stride,
+                               micv_stream stream);
+
 /* ------------------------------------------------------- ps7: central moments ------- */
 
 /* moments::centralMoment (ps7_cpp/lib/Moments.cpp) for `batch` single-channel images: image b starts at

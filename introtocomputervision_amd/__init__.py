@@ -3,12 +3,12 @@
 The product is ``libmicv.so`` (hand-written HIP for gfx950 behind the C ABI declared in
 ``include/mi_cv.h``).  This package is the thin Python host side used by the tests and
 ``bench.py``: a ctypes binding plus modules named after the reference's namespaces
-(``lk``, ``pyr``, ``harris``, ``sift``, ``stereo``, ``hough``, ``warp``, ``ps0``, ``ps1``, ``ps3``, ``ps4``, ``ps5``, ``ps6``).  There is no CPU fallback:
+(``lk``, ``pyr``, ``harris``, ``sift``, ``stereo``, ``hough``, ``warp``, ``ps0``, ``ps1``, ``ps3``, ``ps4``, ``ps5``, ``ps6``, ``ps7``).  There is no CPU fallback:
 importing ``_capi`` fails loudly when the library has not been built.
 """
 __version__ = "0.1.0"
 
-__all__ = ["warp", "ps0", "ps1", "ps3", "ps4", "ps5", "ps6"]
+__all__ = ["warp", "ps0", "ps1", "ps3", "ps4", "ps5", "ps6", "ps7"]
 
 
 def __getattr__(name):

@@ -290,6 +290,13 @@ SIGNATURES = {
     "micv_mhi_history_seq_dev": (i32, [vp, vp, i32, sz, sz, i32, i32, f64, i32, i32, f64, i32, vp, i32, vp, sz, sz,
                                        vp]),
     "micv_mhi_history_seq_host": (i32, [vp, vp, i32, sz, sz, i32, i32, f64, i32, i32, f64, i32, vp, i32, vp, sz, sz]),
+    "micv_mhi_frame_difference_c_dev": (i32, [vp, vp, vp, i32, i32, i32, sz, f64, i32, i32, f64, vp, sz, vp]),
+    "micv_mhi_frame_difference_c_host": (i32, [vp, vp, vp, i32, i32, i32, sz, f64, i32, i32, f64, vp, sz]),
+    "micv_mhi_history_seq_c_dev": (i32, [vp, vp, i32, sz, sz, i32, i32, i32, f64, i32, i32, f64, i32, vp, i32, vp, sz, sz,
+                                         vp, i32, vp, sz, sz, vp]),
+    "micv_mhi_history_seq_c_host": (i32, [vp, vp, i32, sz, sz, i32, i32, i32, f64, i32, i32, f64, i32, vp, i32, vp, sz, sz,
+                                          vp, i32, vp, sz, sz]),
+    "micv_mhi_history_batch_dev": (i32, [vp, vp, vp, sz, sz, i32, i32, i32, i32, vp, vp, vp, i32, i32, f64, vp, sz, sz, vp]),
     "micv_central_moments_dev": (i32, [vp, vp, i32, sz, sz, i32, i32, i32, vp, i32, u32, vp, vp, vp, vp]),
     "micv_central_moments_host": (i32, [vp, vp, i32, sz, sz, i32, i32, i32, vp, i32, u32, vp, vp, vp]),
     "micv_knn_predict_dev": (i32, [vp, vp, i32, sz, vp, vp, i32, sz, i32, i32, u32, vp, vp]),

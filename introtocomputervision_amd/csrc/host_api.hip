@@ -753,6 +753,50 @@ int micv_mhi_history_seq_host(micv_ctx *ctx, const uint8_t *frames, int nframes,
     return h.finish();
 }
 
+int micv_mhi_frame_difference_c_host(micv_ctx *ctx, const uint8_t *f1, const uint8_t *f2, int rows, int cols, int channels,
+                                     size_t stride, double thresh, int blur_w, int blur_h, double blur_sigma, uint8_t *diff,
+                                     size_t dstride) {
+    HostCall h(ctx, "micv_mhi_frame_difference_c_host");
+    if (!h.ok()) return h.finish();
+    MICV_REQUIRE(channels == 1 || channels == 3 || channels == 4, "micv_mhi_frame_difference_c_host: channels %d (1, 3 or 4)", channels);
+    MICV_REQUIRE(f1 && f2 && diff && rows > 0 && cols > 0 && dstride >= (size_t)cols, "micv_mhi_frame_difference_c_host: bad argument");
+    MICV_REQUIRE(stride >= (size_t)cols * channels, "micv_mhi_frame_difference_c_host: stride %zu < cols * channels = %zu", stride,
+                 (size_t)cols * channels);
+    const size_t rb = (size_t)cols * channels;
+    uint8_t *d1 = h.up<uint8_t>(f1, stride, rb, rows), *d2 = h.up<uint8_t>(f2, stride, rb, rows), *dd = h.alloc<uint8_t>((size_t)cols * rows);
+    if (!h.ok()) return h.finish();
+    MICV_TRY(micv_mhi_frame_difference_c_dev(ctx, d1, d2, rows, cols, channels, rb, thresh, blur_w, blur_h, blur_sigma, dd, cols, h.s));
+    h.down(diff, dstride, dd, (size_t)cols, rows);
+    return h.finish();
+}
+
+int micv_mhi_history_seq_c_host(micv_ctx *ctx, const uint8_t *frames, int nframes, size_t frame_pitch, size_t stride, int rows,
+                                int cols, int channels, double thresh, int blur_w, int blur_h, double blur_sigma, int tau,
+                                const int *save, int nsave, uint8_t *out, size_t out_pitch, size_t out_stride,
+                                const int *save_diff, int nsave_diff, uint8_t *diff_out, size_t diff_pitch, size_t diff_stride) {
+    HostCall h(ctx, "micv_mhi_history_seq_c_host");
+    if (!h.ok()) return h.finish();
+    MICV_REQUIRE(channels == 1 || channels == 3 || channels == 4, "micv_mhi_history_seq_c_host: channels %d (1, 3 or 4)", channels);
+    MICV_REQUIRE(frames && nframes >= 2 && rows > 0 && cols > 0 && nsave >= 0 && nsave_diff >= 0 && nsave + nsave_diff >= 1 &&
+                     (nsave == 0 || (save && out)) && (nsave_diff == 0 || (save_diff && diff_out)),
+                 "micv_mhi_history_seq_c_host: bad argument");
+    MICV_REQUIRE(stride >= (size_t)cols * channels && frame_pitch >= stride * (size_t)rows,
+                 "micv_mhi_history_seq_c_host: stride %zu < cols * channels, or frame_pitch below a frame", stride);
+    MICV_REQUIRE((nsave == 0 || (out_stride >= (size_t)cols && (nsave == 1 || out_pitch >= out_stride * (size_t)rows))) &&
+                     (nsave_diff == 0 || (diff_stride >= (size_t)cols && (nsave_diff == 1 || diff_pitch >= diff_stride * (size_t)rows))),
+                 "micv_mhi_history_seq_c_host: bad output stride / pitch");
+    const size_t rb = (size_t)cols * channels, nf = rb * rows, n = (size_t)rows * cols;
+    uint8_t *df = h.alloc<uint8_t>(nf * nframes), *dout = h.alloc<uint8_t>(n * (nsave ? nsave : 1)),
+            *ddiff = h.alloc<uint8_t>(n * (nsave_diff ? nsave_diff : 1));
+    for (int f = 0; f < nframes; f++) h.up_to(df + nf * f, frames + (size_t)f * frame_pitch, stride, rb, rows);
+    if (!h.ok()) return h.finish();
+    MICV_TRY(micv_mhi_history_seq_c_dev(ctx, df, nframes, nf, rb, rows, cols, channels, thresh, blur_w, blur_h, blur_sigma, tau, save,
+                                        nsave, dout, n, cols, save_diff, nsave_diff, ddiff, n, cols, h.s));
+    for (int i = 0; i < nsave; i++) h.down(out + (size_t)i * out_pitch, out_stride, dout + n * i, (size_t)cols, rows);
+    for (int i = 0; i < nsave_diff; i++) h.down(diff_out + (size_t)i * diff_pitch, diff_stride, ddiff + n * i, (size_t)cols, rows);
+    return h.finish();
+}
+
 int micv_central_moments_host(micv_ctx *ctx, const void *imgs, int batch, size_t img_pitch, size_t stride, int rows,
                               int cols, int type, const int *orders, int n, uint32_t flags, float *mu, float *eta,
                               float *raw) {

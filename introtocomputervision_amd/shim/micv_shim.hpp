@@ -714,18 +714,26 @@ inline void disparityNCorr(const Mat &left, const Mat &right, const size_t windo
 
 // ---- "next" rows -----------------------------------------------------------------
 
-namespace mhi {  // ProblemSets/ps7_cpp/include/MotionHistory.h:7-28 (single-channel CV_8U frames)
+namespace mhi {  // ProblemSets/ps7_cpp/include/MotionHistory.h:7-28
 using micv_shim::Mat;
 using micv_shim::Size;
+// CV_8UC1, or the capture's CV_8UC3 / CV_8UC4 (MotionHistory.cpp:50-64: blur and subtract per channel, RGB2GRAY on the
+// difference); ROIs of a larger frame included, the two with one step.  diff is CV_8UC1.
 inline void frameDifference(const Mat &f1, const Mat &f2, const double thresh, Mat &diff,
                             const Size &blurSize = Size(3, 3), const double blurSigma = 1.0) {  // MotionHistory.h:10-15
-    micv_shim::require(f1.type() == micv_shim::U8 && f2.type() == micv_shim::U8 && f1.rows == f2.rows &&
-                           f1.cols == f2.cols && f1.step == f2.step,
-                       "mhi::frameDifference: two CV_8UC1 frames of one size expected");
+    const int cn = f1.channels();
+    micv_shim::require(f1.depth() == micv_shim::U8 && (cn == 1 || cn == 3 || cn == 4) && f2.type() == f1.type() &&
+                           f1.rows == f2.rows && f1.cols == f2.cols && f1.step == f2.step,
+                       "mhi::frameDifference: two CV_8UC1 / CV_8UC3 / CV_8UC4 frames of one type and size expected");
     Mat out(f1.rows, f1.cols, micv_shim::U8);
-    micv_shim::check(micv_mhi_frame_difference_host(micv_shim::context(), f1.ptr<uint8_t>(), f2.ptr<uint8_t>(),
-                                                    f1.rows, f1.cols, f1.step, thresh, blurSize.width,
-                                                    blurSize.height, blurSigma, out.ptr<uint8_t>(), out.step));
+    if (cn == 1)
+        micv_shim::check(micv_mhi_frame_difference_host(micv_shim::context(), f1.ptr<uint8_t>(), f2.ptr<uint8_t>(),
+                                                        f1.rows, f1.cols, f1.step, thresh, blurSize.width,
+                                                        blurSize.height, blurSigma, out.ptr<uint8_t>(), out.step));
+    else
+        micv_shim::check(micv_mhi_frame_difference_c_host(micv_shim::context(), f1.ptr<uint8_t>(), f2.ptr<uint8_t>(),
+                                                          f1.rows, f1.cols, cn, f1.step, thresh, blurSize.width,
+                                                          blurSize.height, blurSigma, out.ptr<uint8_t>(), out.step));
     diff = out;
 }
 inline void calcMotionHistory(Mat &history, const Mat &binaryMask, const int tau) {
