@@ -10,6 +10,7 @@
 
 #include "draw.hpp"
 #include "kernels.hpp"
+#include "pixmap.hpp"
 
 namespace micv {
 
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256) void gauss_f32_tiled_kernel(const float *__res
         float acc = 0.f;
         for (int k = 0; k < t.n; k++) acc = fmaf(R[(ly + k) * GF_TW + lx], t.k[k], acc);
         if (TO_U8)
-            row_ptr(static_cast<uint8_t *>(dst), dstride, y)[x] = f32_to_u8(acc);
+            row_ptr(static_cast<uint8_t *>(dst), dstride, y)[x] = draw::f32_to_u8(acc);
         else
             row_ptr(static_cast<float *>(dst), dstride, y)[x] = acc;
     }
@@ -89,24 +90,6 @@ __global__ __launch_bounds__(256) void erode_ellipse_kernel(const T *__restrict_
         }
         row_ptr(dst, dstride, y)[x] = v;
     }
-}
-
-// ---- cv::cvtColor(GRAY2RGB) to 8 bit
-template <typename T>
-__global__ __launch_bounds__(256) void gray_to_rgb8_kernel(const T *__restrict__ src, size_t stride, int rows, int cols,
-                                                            uint8_t *__restrict__ dst, size_t dstride) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= cols || y >= rows) return;
-    const T t = row_ptr(src, stride, y)[x];
-    uint8_t v;
-    if (sizeof(T) == 4)
-        v = f32_to_u8((float)t);
-    else
-        v = (uint8_t)t;
-    uint8_t *d = row_ptr(dst, dstride, y) + 3 * (size_t)x;
-    d[0] = v;
-    d[1] = v;
-    d[2] = v;
 }
 
 // ---- sol::findParallelLines: one workgroup, all pairs.  keep[i] = some j != i has the key of i; the kept pairs leave in
@@ -157,16 +140,16 @@ __global__ __launch_bounds__(1024) void parallel_lines_kernel(const uint32_t *__
 
 // ---- sol::drawLinesParametric.  blockIdx.y = the peak; a thread is one step along the segment's major axis, and only
 // the steps whose major coordinate lies inside the image are dealt out (the end points of a near-vertical line lie up to
-// ~115 image diagonals outside).  After i major steps of micv_viz::line's walk the minor coordinate has advanced
-// m(i) = (2 minor i + major - 1) div (2 major) (draw.hpp).
+// ~115 image diagonals outside, far inside the narrow walk's bound): draw.hpp.
 struct LineTrig {
     float c[180], s[180];  // cos / sin of the float radian of theta = -90 + i
 };
-__global__ __launch_bounds__(256) void draw_lines_parametric_kernel(uint8_t *__restrict__ img, int rows, int cols, size_t stride,
+__global__ __launch_bounds__(256) void draw_lines_parametric_kernel(uint8_t *__restrict__ pixels, int rows, int cols, size_t stride,
                                                                      const uint32_t *__restrict__ peaks_rc,
                                                                      const int64_t *__restrict__ count_p, unsigned max_peaks,
                                                                      unsigned rho_bin, unsigned theta_bin, long long diag,
-                                                                     LineTrig trig, uint8_t c0, uint8_t c1, uint8_t c2) {
+                                                                     LineTrig trig, uint32_t colour) {
+    const draw::Target img{pixels, stride, rows, cols, 3};  // (3 where put can see it: its byte loop unrolls)
     const int64_t cnt = *count_p;
     if ((int64_t)blockIdx.y >= cnt || blockIdx.y >= max_peaks) return;
     const uint32_t row = peaks_rc[2 * blockIdx.y], col = peaks_rc[2 * blockIdx.y + 1];
@@ -180,48 +163,24 @@ __global__ __launch_bounds__(256) void draw_lines_parametric_kernel(uint8_t *__r
         const float cs = trig.c[theta + 90], sn = trig.s[theta + 90];
         const float slope = (-1.f * cs) / sn, c = frho / sn;  // :102-103
         fx1 = 0.f;
-        fx2 = (float)cols;
+        fx2 = (float)img.cols;
         fy1 = slope * fx1 + c;
         fy2 = slope * fx2 + c;
     } else {
         fy1 = 0.f;
-        fy2 = (float)rows;
+        fy2 = (float)img.rows;
         fx1 = fx2 = frho / trig.c[90];
     }
-    long long x1 = lrintf(fx1), y1 = lrintf(fy1), x2 = lrintf(fx2), y2 = lrintf(fy2);  // Point2f -> Point
-    if (x1 > x2) {
-        long long t = x1; x1 = x2; x2 = t;
-        t = y1; y1 = y2; y2 = t;
-    }
-    const long long dx = x2 - x1, dys = y2 - y1, sy = dys < 0 ? -1 : 1, dy = dys < 0 ? -dys : dys;
-    const bool steep = dy > dx;
-    const long long major = steep ? dy : dx, minor = steep ? dx : dy;
-    // steps whose major coordinate is inside the image
-    long long lo, hi;
-    if (!steep) {
-        lo = -x1;
-        hi = cols - 1 - x1;
-    } else if (sy > 0) {
-        lo = -y1;
-        hi = rows - 1 - y1;
-    } else {
-        lo = y1 - (rows - 1);
-        hi = y1;
-    }
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > major ? major : hi;
-    const long long i = lo + (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i > hi) return;
-    const long long m = line_minor_after(minor, major, i);
-    const long long x = steep ? x1 + m : x1 + i, y = steep ? y1 + sy * i : y1 + sy * m;
-    put_rgb(img, stride, rows, cols, x, y, c0, c1, c2);
+    const draw::LineWalk w = draw::line_walk(img.rows, img.cols, lrintf(fx1), lrintf(fy1), lrintf(fx2), lrintf(fy2));  // Point2f -> Point
+    draw::walk_steps(w, (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256, draw::narrow_minor(w),
+                     [&](long long x, long long y) { draw::put(img, x, y, colour); });
 }
 
-// ---- sol::drawCircles: cv::circle, thickness 1 = the midpoint walk of OpenCV 3.4's drawing.cpp; a thread is a circle.
-__global__ __launch_bounds__(64) void draw_circles_kernel(uint8_t *__restrict__ img, int rows, int cols, size_t stride,
+// ---- sol::drawCircles: cv::circle, thickness 1 (draw.hpp, circle_walk); a thread is a circle.
+__global__ __launch_bounds__(64) void draw_circles_kernel(uint8_t *__restrict__ pixels, int rows, int cols, size_t stride,
                                                            const uint32_t *__restrict__ peaks_rc, const int64_t *__restrict__ counts,
-                                                           unsigned n_radii, unsigned num_peaks, unsigned min_radius, uint8_t c0,
-                                                           uint8_t c1, uint8_t c2) {
+                                                           unsigned n_radii, unsigned num_peaks, unsigned min_radius, uint32_t colour) {
+    const draw::Target img{pixels, stride, rows, cols, 3};
     const unsigned long long t = (unsigned long long)blockIdx.x * 64 + threadIdx.x;
     if (t >= (unsigned long long)n_radii * num_peaks) return;
     const unsigned ri = (unsigned)(t / num_peaks), k = (unsigned)(t - (unsigned long long)ri * num_peaks);
@@ -229,27 +188,17 @@ __global__ __launch_bounds__(64) void draw_circles_kernel(uint8_t *__restrict__ 
     const uint32_t cy_u = peaks_rc[2 * t], cx_u = peaks_rc[2 * t + 1];
     if (cy_u > 65535u || cx_u > 65535u) return;
     const long long cx = cx_u, cy = cy_u, radius = (long long)min_radius + ri;
-    // every pixel of the walk is within 1 of `radius` from the centre: circles that cannot reach the image are skipped
-    if (radius - 1 > cx + cy + rows + cols) return;
-    if (radius + 1 < cx - (cols - 1) || radius + 1 < cy - (rows - 1)) return;
-    long long err = 0, dx = radius, dy = 0, plus = 1, minus = (radius << 1) - 1;
-    while (dx >= dy) {
-        put_rgb(img, stride, rows, cols, cx + dx, cy + dy, c0, c1, c2);
-        put_rgb(img, stride, rows, cols, cx - dx, cy + dy, c0, c1, c2);
-        put_rgb(img, stride, rows, cols, cx + dx, cy - dy, c0, c1, c2);
-        put_rgb(img, stride, rows, cols, cx - dx, cy - dy, c0, c1, c2);
-        put_rgb(img, stride, rows, cols, cx + dy, cy + dx, c0, c1, c2);
-        put_rgb(img, stride, rows, cols, cx - dy, cy + dx, c0, c1, c2);
-        put_rgb(img, stride, rows, cols, cx + dy, cy - dx, c0, c1, c2);
-        put_rgb(img, stride, rows, cols, cx - dy, cy - dx, c0, c1, c2);
-        dy++;
-        err += plus;
-        plus += 2;
-        const long long mask = (err <= 0) - 1;
-        err -= minus & mask;
-        dx += mask;
-        minus -= mask & 2;
-    }
+    if (!draw::circle_reaches(cx, cy, radius, img.rows, img.cols)) return;
+    draw::circle_walk(radius, [&](long long dx, long long dy) {
+        draw::put(img, cx + dx, cy + dy, colour);
+        draw::put(img, cx - dx, cy + dy, colour);
+        draw::put(img, cx + dx, cy - dy, colour);
+        draw::put(img, cx - dx, cy - dy, colour);
+        draw::put(img, cx + dy, cy + dx, colour);
+        draw::put(img, cx - dy, cy + dx, colour);
+        draw::put(img, cx + dy, cy - dx, colour);
+        draw::put(img, cx - dy, cy - dx, colour);
+    });
 }
 
 // cv::getStructuringElement(MORPH_ELLIPSE, Size(k, k)): the half-width of every row, in double as OpenCV computes it
@@ -267,6 +216,9 @@ static bool ellipse_rows(int ksize, EllipseRows *e) {
     }
     return true;
 }
+
+// three colour bytes as put takes them
+static uint32_t bgr_word(const uint8_t *c) { return (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16; }
 
 static bool gauss_ok(int n, double sigma) { return n >= 1 && n <= 31 && (n & 1) && sigma > 0; }
 
@@ -376,22 +328,14 @@ int micv_gray_to_rgb8_dev(micv_ctx *ctx, const void *src, int depth, int rows, i
                      (depth == MICV_DEPTH_8U ? sstride >= (size_t)cols : stride_ok(sstride, cols, 4)),
                  "micv_gray_to_rgb8: bad size / stride");
     MICV_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(cdiv(cols, 64), cdiv(rows, 4));
-    if (depth == MICV_DEPTH_8U)
-        gray_to_rgb8_kernel<uint8_t><<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(src), sstride, rows, cols, dst, dstride);
-    else
-        gray_to_rgb8_kernel<float><<<grid, 256, 0, s>>>(static_cast<const float *>(src), sstride, rows, cols, dst, dstride);
-    MICV_LAUNCH_CHECK();
-    return MICV_OK;
+    return launch_to_bgr8(static_cast<hipStream_t>(stream), src, depth, 1, sstride, rows, cols, dst, dstride);
 }
 
 int micv_draw_lines_parametric_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, size_t stride,
                                    const uint32_t *peaks_rc, const int64_t *count, unsigned max_peaks, unsigned rho_bin,
                                    unsigned theta_bin, const uint8_t *color, micv_stream stream) {
     MICV_REQUIRE(ctx && img && count && color && (peaks_rc || max_peaks == 0), "micv_draw_lines_parametric: null argument");
-    MICV_REQUIRE(rows > 0 && cols > 0 && rows <= 32767 && cols <= 32767 && stride >= (size_t)cols * 3,
-                 "micv_draw_lines_parametric: bad size / stride");
+    MICV_REQUIRE(draw::image_ok(rows, cols, 3, stride, 32767), "micv_draw_lines_parametric: bad size / stride");
     MICV_REQUIRE(max_peaks <= 4096 && rho_bin > 0 && theta_bin > 0, "micv_draw_lines_parametric: bad peak count / bin size");
     if (max_peaks == 0) return MICV_OK;
     MICV_HIP(hipSetDevice(ctx->device));
@@ -403,8 +347,8 @@ int micv_draw_lines_parametric_dev(micv_ctx *ctx, uint8_t *img, int rows, int co
     }
     const int longest = rows > cols ? rows : cols;
     draw_lines_parametric_kernel<<<dim3(cdiv(longest, 256), max_peaks), 256, 0, static_cast<hipStream_t>(stream)>>>(
-        img, rows, cols, stride, peaks_rc, count, max_peaks, rho_bin, theta_bin, (long long)hough_diag(rows, cols), trig, color[0],
-        color[1], color[2]);
+        img, rows, cols, stride, peaks_rc, count, max_peaks, rho_bin, theta_bin, (long long)hough_diag(rows, cols), trig,
+        bgr_word(color));
     MICV_LAUNCH_CHECK();
     return MICV_OK;
 }
@@ -413,15 +357,14 @@ int micv_draw_circles_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, size_
                           const int64_t *counts, unsigned n_radii, unsigned num_peaks, unsigned min_radius,
                           const uint8_t *color, micv_stream stream) {
     MICV_REQUIRE(ctx && img && color, "micv_draw_circles: null argument");
-    MICV_REQUIRE(rows > 0 && cols > 0 && rows <= 32767 && cols <= 32767 && stride >= (size_t)cols * 3,
-                 "micv_draw_circles: bad size / stride");
+    MICV_REQUIRE(draw::image_ok(rows, cols, 3, stride, 32767), "micv_draw_circles: bad size / stride");
     MICV_REQUIRE(num_peaks <= 4096 && (unsigned long long)n_radii * num_peaks < (1ull << 31), "micv_draw_circles: too many circles");
     if (n_radii == 0 || num_peaks == 0) return MICV_OK;
     MICV_REQUIRE(peaks_rc && counts, "micv_draw_circles: null argument");
     MICV_HIP(hipSetDevice(ctx->device));
     const unsigned total = n_radii * num_peaks;
-    draw_circles_kernel<<<cdiv(total, 64), 64, 0, static_cast<hipStream_t>(stream)>>>(img, rows, cols, stride, peaks_rc, counts, n_radii,
-                                                                                     num_peaks, min_radius, color[0], color[1], color[2]);
+    draw_circles_kernel<<<cdiv(total, 64), 64, 0, static_cast<hipStream_t>(stream)>>>(img, rows, cols, stride, peaks_rc, counts,
+                                                                                     n_radii, num_peaks, min_radius, bgr_word(color));
     MICV_LAUNCH_CHECK();
     return MICV_OK;
 }

@@ -6,7 +6,8 @@
 // ("ps3 driver"), PARITY WITH OPENCV'S RASTERISER UNPINNED.  Nothing here synchronises the host or reads an end point on
 // the host.
 //
-// One wave per segment, one lane per step of the walk whose major coordinate is in the image (ps3_lane.hpp).  All strokes
+// One wave per segment, one lane per step of the walk whose major coordinate is in the image (ps3_lane.hpp, over the
+// wide walk of draw.hpp).  All strokes
 // share one colour, so crossing strokes store equal bytes: no owner plane and no atomics, as in ps6.hip.
 #include <climits>
 #include <cmath>
@@ -24,7 +25,8 @@ constexpr int kSegThreads = 256, kWave = 64, kSegWaves = kSegThreads / kWave;
 
 // Segment k: (p[k pitch], p[k pitch + 1]) -> (p[k pitch + off2], p[k pitch + off2 + 1]).
 struct SegJob {
-    SegTarget t;
+    draw::Target t;
+    uint32_t colour;  // draw::pack_colour
     const float *p;
     int n, pitch, off2;
 };
@@ -33,15 +35,15 @@ __global__ void __launch_bounds__(kSegThreads) ps3_segments_kernel(const SegJob 
     const long long k = (long long)blockIdx.x * kSegWaves + threadIdx.x / kWave;
     if (k >= job.n) return;
     const float *e = job.p + (size_t)k * job.pitch;
-    const SegWalk w = seg_walk(job.t.rows, job.t.cols, e[0], e[1], e[job.off2], e[job.off2 + 1]);
-    seg_lane(job.t, w, threadIdx.x % kWave, kWave);
+    seg_lane(job.t, job.colour, e[0], e[1], e[job.off2], e[job.off2 + 1], threadIdx.x % kWave, kWave);
 }
 
 // Both pictures of runProblem2 / runExtraCredit in one launch: waves 0 .. n - 1 draw the lines of image B's points in
 // image A (side 0), waves n .. 2n - 1 the lines of image A's points in image B (side 1).  Each wave computes its end points
 // with the device function of micv_epipolar_endpoints_dev (every lane the same values) and walks them at once.
 struct DisplayJob {
-    SegTarget a, b;
+    draw::Target a, b;
+    uint32_t colour;
     const float *F, *ptsA, *ptsB;  // F 3 x 3; the points n x {x, y}
     int n, f64;
     float *ends;  // [2][n][6] or null
@@ -53,29 +55,18 @@ __global__ void __launch_bounds__(kSegThreads) ps3_display_kernel(const DisplayJ
     const int side = k >= job.n, lane = threadIdx.x % kWave;
     const size_t i = (size_t)(side ? k - job.n : k);
     const float *p = (side ? job.ptsA : job.ptsB) + 2 * i;
-    const SegTarget &t = side ? job.b : job.a;
+    const draw::Target &t = side ? job.b : job.a;
     float e[6];
     if (job.f64) epipolar_endpoints<double>(job.F, p[0], p[1], side, t.rows, t.cols, e);
     else epipolar_endpoints<float>(job.F, p[0], p[1], side, t.rows, t.cols, e);
     if (job.ends && lane == 0)
         for (int c = 0; c < 6; c++) job.ends[((size_t)side * job.n + i) * 6 + c] = e[c];
-    const SegWalk w = seg_walk(t.rows, t.cols, e[0], e[1], e[3], e[4]);
-    seg_lane(t, w, lane, kWave);
+    seg_lane(t, job.colour, e[0], e[1], e[3], e[4], lane, kWave);
 }
 
-// saturate_cast<uchar>(nearbyint(color[k])), k < 4 (NaN gives 0): the colour rule of micv_draw_rectangle_*
-uint32_t pack_colour(const double *c) {
-    uint32_t out = 0;
-    for (int k = 0; k < 4; k++) {
-        const double v = std::nearbyint(c[k]);
-        const uint32_t b = !(v > 0) ? 0u : (v > 255 ? 255u : (uint32_t)v);
-        out |= b << (8 * k);
-    }
-    return out;
-}
-
+// draw.hpp's check with this file's largest side, and a stride that fits 32 bits
 bool image_ok(int rows, int cols, int ch, size_t stride) {
-    return rows > 0 && cols > 0 && rows <= 32768 && cols <= 32768 && stride >= (size_t)cols * ch && stride < (size_t)1 << 32;
+    return draw::image_ok(rows, cols, ch, stride, 32768) && stride < (size_t)1 << 32;
 }
 
 int check_args(const char *fn, micv_ctx *ctx, const uint8_t *img, int rows, int cols, int ch, size_t stride, const float *p, int n,
@@ -91,7 +82,7 @@ int launch_segments(micv_ctx *ctx, uint8_t *img, int rows, int cols, int ch, siz
     if (n == 0) return MICV_OK;
     MICV_HIP(hipSetDevice(ctx->device));
     SegJob job{};
-    job.t.img = img, job.t.stride = stride, job.t.rows = rows, job.t.cols = cols, job.t.ch = ch, job.t.colour = pack_colour(color);
+    job.t = draw::Target{img, stride, rows, cols, ch}, job.colour = draw::pack_colour(color);
     job.p = p, job.n = n, job.pitch = pitch, job.off2 = off2;
     ps3_segments_kernel<<<cdiv((unsigned)n, kSegWaves), kSegThreads, 0, s>>>(job);
     MICV_LAUNCH_CHECK();
@@ -142,9 +133,9 @@ int enqueue_display(micv_ctx *ctx, const float *F, const float *ptsA, const floa
         if (p->out != p->src)
             MICV_HIP(hipMemcpy2DAsync(p->out, p->ostride, p->src, p->sstride, (size_t)p->cols * ch, p->rows, hipMemcpyDeviceToDevice, s));
     DisplayJob job{};
-    const uint32_t c = pack_colour(color);
-    job.a = SegTarget{a.out, a.ostride, a.rows, a.cols, ch, c};
-    job.b = SegTarget{b.out, b.ostride, b.rows, b.cols, ch, c};
+    job.a = draw::Target{a.out, a.ostride, a.rows, a.cols, ch};
+    job.b = draw::Target{b.out, b.ostride, b.rows, b.cols, ch};
+    job.colour = draw::pack_colour(color);
     job.F = F, job.ptsA = ptsA, job.ptsB = ptsB, job.n = n, job.f64 = (flags & MICV_GEOM_F64) ? 1 : 0, job.ends = ends;
     ps3_display_kernel<<<cdiv(2u * (unsigned)n, kSegWaves), kSegThreads, 0, s>>>(job);
     MICV_LAUNCH_CHECK();

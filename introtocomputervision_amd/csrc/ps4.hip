@@ -18,6 +18,7 @@
 
 #include "draw.hpp"
 #include "kernels.hpp"
+#include "pixmap.hpp"
 #include "sincos_deg.hpp"
 
 namespace micv {
@@ -39,38 +40,20 @@ __device__ __forceinline__ int64_t clamp_count(const int64_t *count, int64_t cap
     const int64_t c = count ? *count : 0;
     return c < 0 ? 0 : (c < cap ? c : cap);
 }
-// cvRound of a coordinate: half to even; values that are not finite or beyond 1e9 draw nothing
+// cvRound of a coordinate: half to even; values that are not finite or beyond 1e9 draw nothing.  1e9 < 2^30 =
+// 1 073 741 824, and a glyph's stroke ends within 32767 + 1 of its centre: inside the bound of draw.hpp's narrow walk.
 __device__ __forceinline__ bool coord_ok(float v) { return fabsf(v) < 1e9f; }  // (false for NaN and inf)
 
-// The steps of micv_viz::line(p1, p2) whose major coordinate lies inside a rows x cols image, dealt out to the wave's
-// lanes; every in-image pixel claims its owner word.
+__device__ __forceinline__ void claim(unsigned *owner, int rows, int cols, long long x, long long y, unsigned tag) {
+    if (x >= 0 && x < cols && y >= 0 && y < rows) atomicMax(owner + (size_t)y * cols + (size_t)x, tag);
+}
+
+// The in-image steps of micv_viz::line(p1, p2) (draw.hpp), dealt out to the wave's lanes; every pixel claims its owner word.
 __device__ __forceinline__ void claim_stroke(unsigned *owner, int rows, int cols, long long x1, long long y1, long long x2,
                                              long long y2, unsigned tag) {
-    if (x1 > x2) {
-        long long t = x1; x1 = x2; x2 = t;
-        t = y1; y1 = y2; y2 = t;
-    }
-    const long long dx = x2 - x1, dys = y2 - y1, sy = dys < 0 ? -1 : 1, dy = dys < 0 ? -dys : dys;
-    const bool steep = dy > dx;
-    const long long major = steep ? dy : dx, minor = steep ? dx : dy;
-    long long lo, hi;
-    if (!steep) {
-        lo = -x1;
-        hi = cols - 1 - x1;
-    } else if (sy > 0) {
-        lo = -y1;
-        hi = rows - 1 - y1;
-    } else {
-        lo = y1 - (rows - 1);
-        hi = y1;
-    }
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > major ? major : hi;
-    for (long long i = lo + (threadIdx.x & (kWave - 1)); i <= hi; i += kWave) {
-        const long long m = line_minor_after(minor, major, i);
-        const long long x = steep ? x1 + m : x1 + i, y = steep ? y1 + sy * i : y1 + sy * m;
-        if (x >= 0 && x < cols && y >= 0 && y < rows) atomicMax(owner + (size_t)y * cols + (size_t)x, tag);
-    }
+    const draw::LineWalk w = draw::line_walk(rows, cols, x1, y1, x2, y2);
+    draw::walk_steps(w, threadIdx.x & (kWave - 1), kWave, draw::narrow_minor(w),
+                     [&](long long x, long long y) { claim(owner, rows, cols, x, y, tag); });
 }
 
 // ---- keypoint glyphs ----------------------------------------------------------------------------------------------
@@ -96,25 +79,13 @@ __global__ __launch_bounds__(kWave) void glyph_claim_kernel(unsigned *__restrict
         if (!coord_ok(x) || !coord_ok(y) || !(half >= 0.f && half <= 32767.f)) continue;
         const long long cx = (long long)rintf(x), cy = (long long)rintf(y), radius = (long long)rintf(half);
         const unsigned tag = (unsigned)j + 1u;
-        // the circle: every pixel of the walk is within 1 of `radius` from the centre; the eight points of a step go to
-        // lanes 0..7, which walk the octant together
-        const bool reach = !(radius - 1 > (cx < 0 ? -cx : cx) + (cy < 0 ? -cy : cy) + rows + cols) && !(radius + 1 < cx - (cols - 1)) &&
-                           !(radius + 1 < cy - (rows - 1)) && !(radius + 1 < -cx) && !(radius + 1 < -cy);
-        if (reach && lane < 8) {
+        // the circle (draw.hpp): the eight points of a step go to lanes 0..7, which walk the octant together
+        if (lane < 8 && draw::circle_reaches(cx, cy, radius, rows, cols)) {
             const bool swap = lane & 4;
             const long long sa = (lane & 1) ? -1 : 1, sb = (lane & 2) ? -1 : 1;
-            long long err = 0, dx = radius, dy = 0, plus = 1, minus = (radius << 1) - 1;
-            while (dx >= dy) {
-                const long long px = cx + sa * (swap ? dy : dx), py = cy + sb * (swap ? dx : dy);
-                if (px >= 0 && px < cols && py >= 0 && py < rows) atomicMax(owner + (size_t)py * cols + (size_t)px, tag);
-                dy++;
-                err += plus;
-                plus += 2;
-                const long long mask = (err <= 0) - 1;
-                err -= minus & mask;
-                dx += mask;
-                minus -= mask & 2;
-            }
+            draw::circle_walk(radius, [&](long long dx, long long dy) {
+                claim(owner, rows, cols, cx + sa * (swap ? dy : dx), cy + sb * (swap ? dx : dy), tag);
+            });
         }
         if (angle != -1.f && fabsf(angle) < 1e9f) {  // the orientation stroke
             float s, c;
@@ -125,25 +96,20 @@ __global__ __launch_bounds__(kWave) void glyph_claim_kernel(unsigned *__restrict
     }
 }
 
-// The panel: the source pixel (grey replicated, or BGR; src NULL: what the canvas holds), or the owner's colour.
+// The panel: the owner's colour, or the source pixel as pixmap.hpp copies it (src NULL: what the canvas holds).
 __global__ __launch_bounds__(256) void glyph_resolve_kernel(const uint8_t *__restrict__ src, int channels, size_t sstride, int rows,
                                                              int cols, const unsigned *__restrict__ owner,
                                                              const uint32_t *__restrict__ table, uint8_t *__restrict__ dst,
                                                              size_t dstride) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= cols || y >= rows) return;
-    uint8_t *d = dst + (size_t)y * dstride + 3 * (size_t)x;
-    const unsigned o = owner ? owner[(size_t)y * cols + x] : 0u;
+    const draw::Target panel{dst, dstride, rows, cols, 3};
+    const unsigned o = owner[(size_t)y * cols + x];
     if (o) {
-        const uint32_t c = table[o - 1];
-        d[0] = (uint8_t)c;
-        d[1] = (uint8_t)(c >> 8);
-        d[2] = (uint8_t)(c >> 16);
+        draw::put(panel, x, y, table[o - 1]);
     } else if (src) {
-        const uint8_t *s = src + (size_t)y * sstride + (size_t)channels * x;
-        d[0] = s[0];
-        d[1] = s[channels == 3 ? 1 : 0];
-        d[2] = s[channels == 3 ? 2 : 0];
+        const uint8_t *s = src + (size_t)y * sstride;
+        draw::put(panel, x, y, channels == 3 ? draw::read_bgr<uint8_t, 3>(s, x) : draw::read_bgr<uint8_t, 1>(s, x));
     }
 }
 
@@ -197,17 +163,9 @@ __global__ __launch_bounds__(256) void dots_kernel(const T *__restrict__ gray, s
                                                     size_t mstride, int rows, int cols, uint8_t *__restrict__ dst, size_t dstride) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= cols || y >= rows) return;
-    const T t = reinterpret_cast<const T *>(reinterpret_cast<const char *>(gray) + (size_t)y * gstride)[x];
-    uint8_t v;
-    if (sizeof(T) == 4)
-        v = f32_to_u8((float)t);
-    else
-        v = (uint8_t)t;
+    const T *row = reinterpret_cast<const T *>(reinterpret_cast<const char *>(gray) + (size_t)y * gstride);
     const bool dot = mask[(size_t)y * mstride + x] != 0;
-    uint8_t *d = dst + (size_t)y * dstride + 3 * (size_t)x;
-    d[0] = dot ? (uint8_t)0 : v;
-    d[1] = dot ? (uint8_t)0 : v;
-    d[2] = dot ? (uint8_t)255 : v;
+    draw::put(draw::Target{dst, dstride, rows, cols, 3}, x, y, dot ? 0xFF0000u : draw::read_bgr<T, 1>(row, x));
 }
 
 // x counts BYTES of the destination row
@@ -219,7 +177,7 @@ __global__ __launch_bounds__(256) void hconcat_kernel(const uint8_t *__restrict_
     dst[(size_t)y * dstride + x] = x < abytes ? a[(size_t)y * astride + x] : b[(size_t)y * bstride + (x - abytes)];
 }
 
-bool size_ok(int rows, int cols) { return rows > 0 && cols > 0 && rows <= 32767 && cols <= 32767; }
+constexpr int kMaxSide = 32767;
 constexpr int64_t kMaxStrokes = (int64_t)1 << 24;  // per call: the owner word holds priority + 1
 
 unsigned stroke_waves(int64_t cap) { return (unsigned)std::min<int64_t>(std::max<int64_t>(cap, 1), kMaxStrokeWaves); }
@@ -246,7 +204,7 @@ int micv_draw_dots_dev(micv_ctx *ctx, const void *gray, int depth, int rows, int
                        size_t cstride, uint8_t *dst, size_t dstride, micv_stream stream) {
     MICV_REQUIRE(ctx && gray && corners && dst, "micv_draw_dots: null argument");
     MICV_REQUIRE(depth == MICV_DEPTH_8U || depth == MICV_DEPTH_32F, "micv_draw_dots: depth %d not supported (8U, 32F)", depth);
-    MICV_REQUIRE(size_ok(rows, cols) && stride_ok(gstride, cols, depth == MICV_DEPTH_32F ? 4 : 1) && stride_ok(cstride, cols, 4) &&
+    MICV_REQUIRE(draw::size_ok(rows, cols, kMaxSide) && stride_ok(gstride, cols, depth == MICV_DEPTH_32F ? 4 : 1) && stride_ok(cstride, cols, 4) &&
                      dstride >= (size_t)cols * 3,
                  "micv_draw_dots: bad size %dx%d (1..32767) or stride", rows, cols);
     MICV_REQUIRE(gray != dst && static_cast<const void *>(corners) != dst, "micv_draw_dots: dst aliases an input");
@@ -264,7 +222,7 @@ int micv_hconcat_dev(micv_ctx *ctx, const uint8_t *a, size_t astride, int acols,
                      int rows, int bpp, uint8_t *dst, size_t dstride, micv_stream stream) {
     MICV_REQUIRE(ctx && a && b && dst, "micv_hconcat: null argument");
     MICV_REQUIRE(bpp == 1 || bpp == 3, "micv_hconcat: %d bytes per pixel not supported (1 or 3)", bpp);
-    MICV_REQUIRE(size_ok(rows, acols) && size_ok(rows, bcols), "micv_hconcat: bad size %d x (%d + %d) (1..32767)", rows, acols, bcols);
+    MICV_REQUIRE(draw::size_ok(rows, acols, kMaxSide) && draw::size_ok(rows, bcols, kMaxSide), "micv_hconcat: bad size %d x (%d + %d) (1..32767)", rows, acols, bcols);
     MICV_REQUIRE(astride >= (size_t)acols * bpp && bstride >= (size_t)bcols * bpp && dstride >= ((size_t)acols + bcols) * bpp,
                  "micv_hconcat: a stride is smaller than its row");
     MICV_REQUIRE(a != dst && b != dst, "micv_hconcat: dst aliases an input");
@@ -282,7 +240,7 @@ int micv_draw_keypoints_dev(micv_ctx *ctx, const uint8_t *src, int channels, int
     MICV_REQUIRE(cap >= 0 && cap <= kMaxStrokes && (cap == 0 || (kp_xysa && count)),
                  "micv_draw_keypoints: cap %lld out of 0..2^24, or keypoints / count missing", (long long)cap);
     MICV_REQUIRE(!src || channels == 1 || channels == 3, "micv_draw_keypoints: %d channels not supported (1 or 3)", channels);
-    MICV_REQUIRE(size_ok(rows, cols) && (!src || sstride >= (size_t)cols * channels), "micv_draw_keypoints: bad size %dx%d or stride",
+    MICV_REQUIRE(draw::size_ok(rows, cols, kMaxSide) && (!src || sstride >= (size_t)cols * channels), "micv_draw_keypoints: bad size %dx%d or stride",
                  rows, cols);
     MICV_REQUIRE(x0 >= 0 && canvas_cols <= 65534 && (int64_t)x0 + cols <= canvas_cols && cstride >= (size_t)canvas_cols * 3 &&
                      cstride < (size_t)1 << 32,
@@ -293,13 +251,8 @@ int micv_draw_keypoints_dev(micv_ctx *ctx, const uint8_t *src, int channels, int
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t *panel = canvas + 3 * (size_t)x0;
     const dim3 grid(cdiv(cols, 64), cdiv(rows, 4));
-    if (cap == 0) {  // the copy alone
-        if (src) {
-            glyph_resolve_kernel<<<grid, 256, 0, s>>>(src, channels, sstride, rows, cols, nullptr, nullptr, panel, cstride);
-            MICV_LAUNCH_CHECK();
-        }
-        return MICV_OK;
-    }
+    if (cap == 0)  // the copy alone
+        return src ? launch_to_bgr8(s, src, MICV_DEPTH_8U, channels, sstride, rows, cols, panel, cstride) : MICV_OK;
     const size_t npix = (size_t)rows * cols;
     void *scratch;
     MICV_TRY(ctx->reserve(Carver::need(npix, 4) + Carver::need((size_t)cap, 4), &scratch));
@@ -350,7 +303,7 @@ int micv_ps4_harris_display_dev(micv_ctx *ctx, const float *img, int rows, int c
                                 int32_t *locs_yx, int64_t cap, int64_t *count, uint8_t *grad_panel, size_t gstride,
                                 uint8_t *resp_u8, size_t rstride, uint8_t *dots, size_t dstride, micv_stream stream) {
     MICV_REQUIRE(ctx && img && fields && grad_panel && resp_u8 && dots, "micv_ps4_harris_display: null argument");
-    MICV_REQUIRE(size_ok(rows, cols) && stride_ok(stride, cols, 4) && gstride >= (size_t)2 * cols && gstride < (size_t)1 << 32 &&
+    MICV_REQUIRE(draw::size_ok(rows, cols, kMaxSide) && stride_ok(stride, cols, 4) && gstride >= (size_t)2 * cols && gstride < (size_t)1 << 32 &&
                      rstride >= (size_t)cols && dstride >= (size_t)cols * 3,
                  "micv_ps4_harris_display: bad size %dx%d or stride", rows, cols);
     MICV_HIP(hipSetDevice(ctx->device));
@@ -377,7 +330,7 @@ int micv_ps4_match_panels_dev(micv_ctx *ctx, const uint8_t *img_a, size_t astrid
                               uint8_t *keypoint_panel, uint8_t *match_panel, size_t pstride, micv_stream stream) {
     MICV_REQUIRE(ctx && img_a && img_b && match_panel && rng_state, "micv_ps4_match_panels: null argument");
     MICV_REQUIRE((flags & ~MICV_PS4_NO_GLYPHS) == 0, "micv_ps4_match_panels: unknown flag in %d", flags);
-    MICV_REQUIRE(size_ok(rows, cols_a) && size_ok(rows, cols_b) && astride >= (size_t)cols_a && bstride >= (size_t)cols_b,
+    MICV_REQUIRE(draw::size_ok(rows, cols_a, kMaxSide) && draw::size_ok(rows, cols_b, kMaxSide) && astride >= (size_t)cols_a && bstride >= (size_t)cols_b,
                  "micv_ps4_match_panels: bad size %d x (%d + %d) or stride", rows, cols_a, cols_b);
     MICV_REQUIRE(keypoint_panel != match_panel, "micv_ps4_match_panels: the two panels alias");
     const bool glyphs = !(flags & MICV_PS4_NO_GLYPHS);

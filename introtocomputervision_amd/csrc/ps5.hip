@@ -14,6 +14,7 @@
 #include "kernels.hpp"
 #include "lk_device.hpp"
 #include "minmax_keys.hpp"
+#include "pixmap.hpp"
 
 namespace micv {
 namespace {
@@ -30,37 +31,14 @@ struct ArrowArgs {
     const float *u, *v;
     size_t field_pitch, fstride;  // bytes
     int rows, cols, row_step, col_step, nx;
-    uint8_t c0, c1, c2;
+    uint32_t colour;  // B, G, R in bits 0, 8, 16
 };
 
-// micv_viz::line(p1, p2): the walk's pixels with their major coordinate inside the image, dealt out to the wave's lanes
-__device__ __forceinline__ void stroke(uint8_t *img, size_t stride, int rows, int cols, long long x1, long long y1, long long x2,
-                                       long long y2, uint8_t c0, uint8_t c1, uint8_t c2) {
-    if (x1 > x2) {
-        long long t = x1; x1 = x2; x2 = t;
-        t = y1; y1 = y2; y2 = t;
-    }
-    const long long dx = x2 - x1, dys = y2 - y1, sy = dys < 0 ? -1 : 1, dy = dys < 0 ? -dys : dys;
-    const bool steep = dy > dx;
-    const long long major = steep ? dy : dx, minor = steep ? dx : dy;
-    long long lo, hi;
-    if (!steep) {
-        lo = -x1;
-        hi = cols - 1 - x1;
-    } else if (sy > 0) {
-        lo = -y1;
-        hi = rows - 1 - y1;
-    } else {
-        lo = y1 - (rows - 1);
-        hi = y1;
-    }
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > major ? major : hi;
-    for (long long i = lo + threadIdx.x; i <= hi; i += kArrowThreads) {
-        const long long m = line_minor_after(minor, major, i);
-        const long long x = steep ? x1 + m : x1 + i, y = steep ? y1 + sy * i : y1 + sy * m;
-        put_rgb(img, stride, rows, cols, x, y, c0, c1, c2);
-    }
+// micv_viz::line(p1, p2): the in-image steps of the walk (draw.hpp), dealt out to the wave's lanes.  Every coordinate is
+// below 1e6 + cols + a tip of a tenth of the shaft, far inside the narrow walk's bound.
+__device__ __forceinline__ void stroke(const draw::Target &t, long long x1, long long y1, long long x2, long long y2, uint32_t colour) {
+    const draw::LineWalk w = draw::line_walk(t.rows, t.cols, x1, y1, x2, y2);
+    draw::walk_steps(w, threadIdx.x, kArrowThreads, draw::narrow_minor(w), [&](long long x, long long y) { draw::put(t, x, y, colour); });
 }
 
 __global__ __launch_bounds__(kArrowThreads) void velocity_vectors_kernel(const ArrowArgs g) {
@@ -70,32 +48,19 @@ __global__ __launch_bounds__(kArrowThreads) void velocity_vectors_kernel(const A
     const float uVal = reinterpret_cast<const float *>(reinterpret_cast<const char *>(g.u) + foff)[x];
     const float vVal = reinterpret_cast<const float *>(reinterpret_cast<const char *>(g.v) + foff)[x];
     if (!isfinite(uVal) || !isfinite(vVal) || fabsf(uVal) > 1e6f || fabsf(vVal) > 1e6f) return;
-    uint8_t *img = g.img + (size_t)blockIdx.y * g.img_pitch;
+    const draw::Target img{g.img + (size_t)blockIdx.y * g.img_pitch, g.stride, g.rows, g.cols, 3};
     // micv_viz::arrowed_line(x, y, x + u, y + v): the float32 sums, rounded half to even (|value| <= 1e6 + cols: an int)
     const float x2f = (float)x + uVal, y2f = (float)y + vVal;
     const long long p1x = x, p1y = y, p2x = (long long)rintf(x2f), p2y = (long long)rintf(y2f);
     const double ddx = (double)p1x - (double)p2x, ddy = (double)p1y - (double)p2y;
     const double tip = sqrt(ddx * ddx + ddy * ddy) * 0.1;
-    stroke(img, g.stride, g.rows, g.cols, p1x, p1y, p2x, p2y, g.c0, g.c1, g.c2);
+    stroke(img, p1x, p1y, p2x, p2y, g.colour);
     const double angle = atan2(ddy, ddx), q = 3.14159265358979323846 / 4;
     long long px = (long long)rint((double)p2x + tip * cos(angle + q)), py = (long long)rint((double)p2y + tip * sin(angle + q));
-    stroke(img, g.stride, g.rows, g.cols, px, py, p2x, p2y, g.c0, g.c1, g.c2);
+    stroke(img, px, py, p2x, p2y, g.colour);
     px = (long long)rint((double)p2x + tip * cos(angle - q));
     py = (long long)rint((double)p2y + tip * sin(angle - q));
-    stroke(img, g.stride, g.rows, g.cols, px, py, p2x, p2y, g.c0, g.c1, g.c2);
-}
-
-// ---- prevImg.clone() and, for a grey frame, cv::cvtColor(GRAY2RGB): the image the arrows are drawn on
-template <int CN>
-__global__ __launch_bounds__(256) void to_bgr8_kernel(const uint8_t *__restrict__ src, size_t sstride, int rows, int cols,
-                                                       uint8_t *__restrict__ dst, size_t dstride) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= cols || y >= rows) return;
-    const uint8_t *s = src + (size_t)y * sstride + (size_t)CN * x;
-    uint8_t *d = dst + (size_t)y * dstride + 3 * (size_t)x;
-    d[0] = s[0];
-    d[1] = s[CN == 3 ? 1 : 0];
-    d[2] = s[CN == 3 ? 2 : 0];
+    stroke(img, px, py, p2x, p2y, g.colour);
 }
 
 // ---- savePyramid.  Launch 1: the ranges of the four levels (blockIdx.y = level), kept as display.hip keeps them: order-
@@ -188,7 +153,7 @@ __global__ __launch_bounds__(256) void warp_diff_kernel(const float *__restrict_
     diff[(size_t)y * dstride + x] = prev[(size_t)y * pstride + x] - w;
 }
 
-bool size_ok(int rows, int cols) { return rows > 0 && cols > 0 && rows <= 32767 && cols <= 32767; }
+constexpr int kMaxSide = 32767;
 
 }  // namespace
 }  // namespace micv
@@ -201,7 +166,7 @@ int micv_draw_velocity_vectors_dev(micv_ctx *ctx, uint8_t *img, size_t img_pitch
                                    size_t field_pitch, size_t fstride, int batch, int rows, int cols, const uint8_t *color,
                                    micv_stream stream) {
     MICV_REQUIRE(ctx && img && u && v && color, "micv_draw_velocity_vectors: null argument");
-    MICV_REQUIRE(size_ok(rows, cols), "micv_draw_velocity_vectors: bad size %dx%d (1..32767)", rows, cols);
+    MICV_REQUIRE(draw::size_ok(rows, cols, kMaxSide), "micv_draw_velocity_vectors: bad size %dx%d (1..32767)", rows, cols);
     MICV_REQUIRE(stride >= (size_t)cols * 3 && stride < (size_t)1 << 32 && stride_ok(fstride, cols, 4),
                  "micv_draw_velocity_vectors: the image's stride %zu or the fields' stride %zu does not hold %d columns", stride,
                  fstride, cols);
@@ -218,7 +183,7 @@ int micv_draw_velocity_vectors_dev(micv_ctx *ctx, uint8_t *img, size_t img_pitch
     g.row_step = rows / 30 > 1 ? rows / 30 : 1;  // Solution.cpp:22-23; images under 30 pixels: 1, as micv_viz
     g.col_step = cols / 30 > 1 ? cols / 30 : 1;
     g.nx = (int)cdiv(cols, g.col_step);
-    g.c0 = color[0]; g.c1 = color[1]; g.c2 = color[2];
+    g.colour = (uint32_t)color[0] | (uint32_t)color[1] << 8 | (uint32_t)color[2] << 16;
     const unsigned arrows = cdiv(rows, g.row_step) * (unsigned)g.nx;  // at most 59 * 59
     velocity_vectors_kernel<<<dim3(arrows, batch), kArrowThreads, 0, static_cast<hipStream_t>(stream)>>>(g);
     MICV_LAUNCH_CHECK();
@@ -234,14 +199,8 @@ int micv_gray_or_bgr_to_bgr8_dev(micv_ctx *ctx, const void *src, int depth, int 
                  "micv_gray_or_bgr_to_bgr8: bad size %dx%d or stride", rows, cols);
     MICV_REQUIRE(src != dst, "micv_gray_or_bgr_to_bgr8: src and dst alias");
     MICV_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(cdiv(cols, 64), cdiv(rows, 4));
-    if (channels == 1)
-        to_bgr8_kernel<1><<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(src), sstride, rows, cols, dst, dstride);
-    else
-        to_bgr8_kernel<3><<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(src), sstride, rows, cols, dst, dstride);
-    MICV_LAUNCH_CHECK();
-    return MICV_OK;
+    // prevImg.clone() and, for a grey frame, cv::cvtColor(GRAY2RGB): the image the arrows are drawn on
+    return launch_to_bgr8(static_cast<hipStream_t>(stream), src, depth, channels, sstride, rows, cols, dst, dstride);
 }
 
 int micv_pyramid_montage_dev(micv_ctx *ctx, const void *const *levels, const int *level_rows, const int *level_cols,
@@ -290,7 +249,7 @@ int micv_pyramid_montage_dev(micv_ctx *ctx, const void *const *levels, const int
 int micv_lk_warp_diff_dev(micv_ctx *ctx, const float *prev, size_t pstride, const float *next, size_t nstride, const float *du,
                           const float *dv, size_t fstride, int rows, int cols, float *diff, size_t dstride, micv_stream stream) {
     MICV_REQUIRE(ctx && prev && next && du && dv && diff, "micv_lk_warp_diff: null argument");
-    MICV_REQUIRE(size_ok(rows, cols), "micv_lk_warp_diff: bad size %dx%d", rows, cols);
+    MICV_REQUIRE(draw::size_ok(rows, cols, kMaxSide), "micv_lk_warp_diff: bad size %dx%d", rows, cols);
     MICV_REQUIRE(stride_ok(pstride, cols, 4) && stride_ok(nstride, cols, 4) && stride_ok(fstride, cols, 4) && stride_ok(dstride, cols, 4),
                  "micv_lk_warp_diff: bad stride");
     // (the kernel promises __restrict__ on every pointer; next is read at other pixels than the one written)
@@ -307,7 +266,7 @@ int micv_ps5_warp_diff_seq_dev(micv_ctx *ctx, const float *frames, size_t frame_
                                float *u, float *v, micv_stream stream) {
     MICV_REQUIRE(ctx && frames && diff_u8, "micv_ps5_warp_diff_seq: null argument");
     MICV_REQUIRE(nframes >= 2 && nframes <= 1025, "micv_ps5_warp_diff_seq: %d frames (2..1025: at least one pair)", nframes);
-    MICV_REQUIRE(size_ok(rows, cols) && stride_ok(stride, cols, 4), "micv_ps5_warp_diff_seq: bad size %dx%d or stride", rows, cols);
+    MICV_REQUIRE(draw::size_ok(rows, cols, kMaxSide) && stride_ok(stride, cols, 4), "micv_ps5_warp_diff_seq: bad size %dx%d or stride", rows, cols);
     MICV_REQUIRE(frame_pitch % 4 == 0 && frame_pitch >= (size_t)(rows - 1) * stride + (size_t)cols * 4,
                  "micv_ps5_warp_diff_seq: the frame pitch is smaller than a frame");
     MICV_REQUIRE((u == nullptr) == (v == nullptr), "micv_ps5_warp_diff_seq: give both flow outputs or none");
@@ -347,7 +306,7 @@ int micv_dense_lk_display_dev(micv_ctx *ctx, const void *prev, const void *next,
     MICV_REQUIRE(depth == MICV_DEPTH_8U, "micv_dense_lk_display: depth %d not supported (8-bit frames)", depth);
     MICV_REQUIRE(channels == 1 || channels == 3, "micv_dense_lk_display: %d channels not supported (1 or 3)", channels);
     MICV_REQUIRE(mode == MICV_LK_NAIVE || mode == MICV_LK_PYRAMIDAL, "micv_dense_lk_display: mode %d is neither naive (0) nor pyramidal (1)", mode);
-    MICV_REQUIRE(size_ok(rows, cols) && stride >= (size_t)cols * channels && stride_ok(ostride, cols, 4) &&
+    MICV_REQUIRE(draw::size_ok(rows, cols, kMaxSide) && stride >= (size_t)cols * channels && stride_ok(ostride, cols, 4) &&
                      astride >= (size_t)cols * 3 && astride < (size_t)1 << 32,
                  "micv_dense_lk_display: bad size %dx%d or stride", rows, cols);
     MICV_REQUIRE((jet_u == nullptr) == (jet_v == nullptr) && (!jet_u || (jstride >= (size_t)cols * 3 && jstride < (size_t)1 << 32)),

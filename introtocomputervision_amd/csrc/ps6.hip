@@ -16,7 +16,6 @@
 #include <cmath>
 #include <vector>
 
-#include "draw.hpp"
 #include "pf.hpp"
 #include "ps6_lane.hpp"
 
@@ -29,23 +28,13 @@ __global__ void __launch_bounds__(kOverlayThreads) ps6_overlay_kernel(const Over
     overlay_lane(o, (long long)blockIdx.x * kOverlayThreads + threadIdx.x);
 }
 
-// saturate_cast<uchar>(nearbyint(color[k])), k < 4 (NaN gives 0)
-uint32_t pack_colour(const double *c) {
-    uint32_t out = 0;
-    for (int k = 0; k < 4; k++) {
-        const double v = std::nearbyint(c[k]);
-        const uint32_t b = !(v > 0) ? 0u : (v > 255 ? 255u : (uint32_t)v);
-        out |= b << (8 * k);
-    }
-    return out;
-}
-
+// draw.hpp's check with this file's largest side, and a stride that fits 32 bits
 bool image_ok(int rows, int cols, int ch, size_t stride) {
-    return rows > 0 && cols > 0 && rows <= 32767 && cols <= 32767 && stride >= (size_t)cols * ch && stride < (size_t)1 << 32;
+    return draw::image_ok(rows, cols, ch, stride, 32767) && stride < (size_t)1 << 32;
 }
 
 int launch_overlay(const Overlay &o, hipStream_t s) {
-    const long long lanes = (long long)o.n + (o.ring ? 2LL * o.cols + 2LL * o.rows : 0);
+    const long long lanes = (long long)o.n + (o.ring ? 2LL * o.t.cols + 2LL * o.t.rows : 0);
     if (lanes == 0) return MICV_OK;
     ps6_overlay_kernel<<<cdiv((unsigned)lanes, kOverlayThreads), kOverlayThreads, 0, s>>>(o);
     MICV_LAUNCH_CHECK();
@@ -54,10 +43,10 @@ int launch_overlay(const Overlay &o, hipStream_t s) {
 
 Overlay pf_overlay(micv_pf *pf, uint8_t *frame, size_t stride, const double *dot, float bw, float bh, const double *box) {
     Overlay o{};
-    o.img = frame, o.stride = stride, o.rows = pf->rows, o.cols = pf->cols, o.ch = pf->ch;
+    o.t = draw::Target{frame, stride, pf->rows, pf->cols, pf->ch};
     o.xy = reinterpret_cast<const float *>(pf->parts), o.n = pf->n;
     o.ring = 2, o.centre = &pf->state->x, o.bw = bw, o.bh = bh;
-    o.dot = pack_colour(dot), o.box = pack_colour(box);
+    o.dot = draw::pack_colour(dot), o.box = draw::pack_colour(box);
     return o;
 }
 
@@ -86,8 +75,8 @@ int micv_draw_particles_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, int
                  stride);
     MICV_HIP(hipSetDevice(ctx->device));
     Overlay o{};
-    o.img = img, o.stride = stride, o.rows = rows, o.cols = cols, o.ch = channels, o.xy = xy, o.n = n;
-    o.dot = pack_colour(color);
+    o.t = draw::Target{img, stride, rows, cols, channels}, o.xy = xy, o.n = n;
+    o.dot = draw::pack_colour(color);
     return launch_overlay(o, static_cast<hipStream_t>(stream));
 }
 
@@ -99,9 +88,9 @@ int micv_draw_rectangle_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, int
                  stride);
     MICV_HIP(hipSetDevice(ctx->device));
     Overlay o{};
-    o.img = img, o.stride = stride, o.rows = rows, o.cols = cols, o.ch = channels;
+    o.t = draw::Target{img, stride, rows, cols, channels};
     o.ring = 1, o.x = x, o.y = y, o.w = w, o.h = h;
-    o.box = pack_colour(color);
+    o.box = draw::pack_colour(color);
     return launch_overlay(o, static_cast<hipStream_t>(stream));
 }
 
@@ -115,9 +104,9 @@ int micv_ps6_overlay_list_dev(micv_ctx *ctx, uint8_t *img, int rows, int cols, i
                  stride);
     MICV_HIP(hipSetDevice(ctx->device));
     Overlay o{};
-    o.img = img, o.stride = stride, o.rows = rows, o.cols = cols, o.ch = channels, o.xy = xy, o.n = n;
+    o.t = draw::Target{img, stride, rows, cols, channels}, o.xy = xy, o.n = n;
     o.ring = 2, o.centre = centre, o.bw = bbox_w, o.bh = bbox_h;
-    o.dot = pack_colour(dot_color), o.box = pack_colour(box_color);
+    o.dot = draw::pack_colour(dot_color), o.box = draw::pack_colour(box_color);
     return launch_overlay(o, static_cast<hipStream_t>(stream));
 }
 

@@ -46,11 +46,10 @@ static uint32_t pack(const micv_shim::Scalar &c) {
     return out;
 }
 static void run_lanes(Mat &img, const std::vector<float> &seg, int n, const micv_shim::Scalar &colour) {
-    const micv::SegTarget t{img.data, img.step, img.rows, img.cols, img.channels(), pack(colour)};
+    const micv::draw::Target t{img.data, img.step, img.rows, img.cols, img.channels()};
     for (int k = 0; k < n; k++) {
         const float *s = &seg[4 * (size_t)k];
-        const micv::SegWalk w = micv::seg_walk(img.rows, img.cols, s[0], s[1], s[2], s[3]);
-        for (int lane = 0; lane < 64; lane++) micv::seg_lane(t, w, lane, 64);
+        for (int lane = 0; lane < 64; lane++) micv::seg_lane(t, pack(colour), s[0], s[1], s[2], s[3], lane, 64);
     }
 }
 

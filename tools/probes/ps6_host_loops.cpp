@@ -111,17 +111,10 @@ static ParticleFilter filter_with(const std::vector<float> &xy, int rows, int co
 
 static const int kRows = 37, kCols = 53;
 
-// The launch of csrc/ps6.hip, lane by lane: colours packed as pack_colour does, 256 lanes per workgroup.
-static uint32_t pack(const micv_shim::Scalar &c) {
-    uint32_t out = 0;
-    for (int k = 0; k < 4; k++) {
-        const double v = std::nearbyint(c.val[k]);
-        out |= (!(v > 0) ? 0u : (v > 255 ? 255u : (uint32_t)v)) << (8 * k);
-    }
-    return out;
-}
+// The launch of csrc/ps6.hip, lane by lane: colours packed by its pack_colour, 256 lanes per workgroup.
+static uint32_t pack(const micv_shim::Scalar &c) { return micv::draw::pack_colour(c.val); }
 static void run_lanes(micv::Overlay o) {
-    const long long lanes = (long long)o.n + (o.ring ? 2LL * o.cols + 2LL * o.rows : 0);
+    const long long lanes = (long long)o.n + (o.ring ? 2LL * o.t.cols + 2LL * o.t.rows : 0);
     for (long long i = 0; i < (lanes + 255) / 256 * 256; i++) micv::overlay_lane(o, i);
 }
 
@@ -175,7 +168,7 @@ int main(int argc, char **argv) {
             Image img(kRows, kCols, ch, pad);
             if (lanes) {
                 micv::Overlay o{};
-                o.img = img.view.data, o.stride = img.view.step, o.rows = kRows, o.cols = kCols, o.ch = ch;
+                o.t = micv::draw::Target{img.view.data, img.view.step, kRows, kCols, ch};
                 o.xy = xy.data(), o.n = dots ? n : 0;
                 o.ring = box ? 2 : 0, o.centre = b.data(), o.bw = b[2], o.bh = b[3];
                 o.dot = pack(dot), o.box = pack(bc);
@@ -199,7 +192,7 @@ int main(int argc, char **argv) {
             Image img(kRows, kCols, ch, pad);
             if (lanes) {
                 micv::Overlay o{};
-                o.img = img.view.data, o.stride = img.view.step, o.rows = kRows, o.cols = kCols, o.ch = ch;
+                o.t = micv::draw::Target{img.view.data, img.view.step, kRows, kCols, ch};
                 o.ring = 1, o.x = x, o.y = y, o.w = w, o.h = h, o.box = pack(bc);
                 run_lanes(o);
                 img.write(dir + "/" + name + ".u8");
