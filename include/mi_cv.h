@@ -68,8 +68,8 @@ size_t micv_ctx_scratch_bytes(const micv_ctx *ctx);
 #define MICV_OPT_LK_BUILD_OVERLAP  14 /* fused LK, window 15, >= 3 levels: no pyramid-build launch -- the top level reads level 0 itself and the launch of every level k >= 2 carries the build of level k - 1 as extra workgroups behind its tiles: 0 = for single pairs only (default: the latency case; with several passes in flight a batch is faster with the build launch), -1 = never, 1 = for every batch */
 #define MICV_OPT_LK_SPLIT          15 /* fused LK, window 15: a level launch SPLIT in two (r05, lk_split.hip) -- a pre-pass (pyrUp + warp + Sobel once per pixel, Ix / Iy / It into padded planes in HBM) plus a streaming window-sum kernel that carries its row-pass rows from block to block: 0 = never (default: measured 28-42 % slower than the fused launch, HBM traffic 2.4-3x), 1 = every whole-frame launch of at least 64 x 64 with a doubling coarse flow, 2 = 1 with the base flow through u, v, 3 = the pre-pass leaves only the warped image and the second half is the fused kernel in its no-flow mode */
 #define MICV_OPT_LK_STRIP          16 /* fused LK, window 15: the INTERIOR tiles of a level launch as vertical strips that a workgroup streams down in blocks of 16 rows, carrying the last 14 row-pass rows of the five product fields and two warped rows from block to block (lk_strip.hpp) -- no vertical halo recomputation; the border tiles of the same launch stay tiles: 0 = off (default: 15 % fewer instructions, the same time -- DESIGN.md section 5), n > 0 = on with row segments of n blocks (16 = 256 rows); + 8192 = only for launches of 4096 tiles or more */
-#define MICV_OPT_STEREO_EXACT      17 /* disparitySSD on 8-bit-valued images (integers 0..255 in both f32 images, radius <= 7; serial:: semantics radius <= 5): 0 = the exact-sum kernels (stereo_exact.hip: integer dot products, sliding window sums, lanes = disparities), chosen on the device per call by a pre-pass that tests every pixel (default); -1 = always the float kernels that add every window in the contract's order.  Same disparities either way: all sums are integers below 2^24, exact in f32 in any order.  (disparityNCorr always takes the float kernels.) */
-#define MICV_OPT_STEREO_BATCH_MB   18 /* micv_disparity_ssd_u8_batch_dev: MiB of packed planes one launch may hold before the batch is processed in pieces: 0 = 64 (default), n = 1..4096 */
+#define MICV_OPT_STEREO_EXACT      17 /* disparitySSD on 8-bit-valued images (integers 0..255 in both f32 images, radius <= 7; serial:: semantics radius <= 5): 0 = the exact-sum kernels (stereo_exact.hip: integer dot products, sliding window sums, lanes = disparities), chosen on the device per call by a pre-pass that tests every pixel (default); -1 = always the float kernels that add every window in the contract's order.  Same disparities either way: all sums are integers below 2^24, exact in f32 in any order.  (disparityNCorr always takes the float kernels; its u8 entries, micv_disparity_ncorr_u8_*, take the byte-reading float kernels of stereo_ncc_u8.hip.) */
+#define MICV_OPT_STEREO_BATCH_MB   18 /* micv_disparity_ssd_u8_batch_dev: MiB of packed planes one launch may hold before the batch is processed in pieces: 0 = 64 (default), n = 1..4096; micv_disparity_ncorr_u8_batch_dev: the same bound on a launch's f32 window-energy planes (NCC, radius 1..10 without ROLLING) */
 #define MICV_OPT_COUNT            19
 int micv_ctx_set_option(micv_ctx *ctx, int option, int value);
 int micv_ctx_get_option(const micv_ctx *ctx, int option, int *value);
@@ -490,6 +490,38 @@ int micv_disparity_ssd_u8_batch_dev(micv_ctx *ctx, const uint8_t *left, size_t l
                                     const uint8_t *right, size_t rpair_stride, size_t rstride, int batch, int rows, int cols,
                                     int window_rad, int min_disparity, int max_disparity, int flags, int8_t *disp,
                                     size_t dpair_stride, size_t dstride, micv_stream stream);
+/* disparityNCorr on 8-BIT images, with the arguments of the SSD u8 entries above (main.cpp:227-229, 304-306 convertTo(CV_32FC1)
+ * only because cuda::disparityNCorr asserts that type).
+ *
+ * Contract.  For every argument set micv_disparity_ncorr_dev accepts (radius 0..31; COLS_2R, MIN_SSD_5E6, ROLLING; SERIAL is
+ * refused with MICV_EINVAL before anything runs), disp is byte-identical to micv_disparity_ncorr_dev on the two images
+ * converted to f32.  Each image has its own row pitch in bytes (>= cols); pointers and pitches need NO alignment.  Bytes of
+ * disp outside rows x cols, and the gaps between a batch's maps, are not written.  No entry synchronises the host, and none
+ * reads or writes the context's stereo flag word.  batch < 1 and overlapping maps are refused with MICV_EINVAL.
+ *
+ * Dispatch, decided on the host:
+ *   - radius 1..10 without ROLLING (the tile forms): the float search itself reads the bytes (stereo_ncc_u8.hip) -- one
+ *     launch for the window energy of `right`, one for the search, bytes converted to f32 as they are staged in registers
+ *     and LDS.  Device memory holds the bytes and one f32 energy plane per pair (the context's arena), no f32 image.  On
+ *     bytes every operand is in the range of the short exact sqrt / division (ncc_arith.hpp), so that form is compiled in
+ *     and the per-value range tracking of the f32 kernel is not.
+ *   - radius 0, 11..31 and ROLLING: the pair is converted to f32 in the context's scratch and handed to
+ *     micv_disparity_ncorr_dev, pair by pair.
+ *
+ * Batch: the pair is a grid dimension of both launches.  Element i is byte-identical to the single call on pair i.  A
+ * batch whose energy planes pass 64 MiB (MICV_OPT_STEREO_BATCH_MB) goes in pieces, one after the other on the stream: a
+ * piece is as many pairs as keep its planes within the bound, one at least and 65535 at most. */
+int micv_disparity_ncorr_u8_dev(micv_ctx *ctx, const uint8_t *left, size_t lstride, const uint8_t *right, size_t rstride,
+                                int rows, int cols, int window_rad, int min_disparity, int max_disparity, int flags,
+                                int8_t *disp, size_t dstride, micv_stream stream);
+/* Uploads 1 B per pixel and image (micv_disparity_ncorr_host: 4). */
+int micv_disparity_ncorr_u8_host(micv_ctx *ctx, const uint8_t *left, size_t lstride, const uint8_t *right, size_t rstride,
+                                 int rows, int cols, int window_rad, int min_disparity, int max_disparity, int flags,
+                                 int8_t *disp, size_t dstride);
+int micv_disparity_ncorr_u8_batch_dev(micv_ctx *ctx, const uint8_t *left, size_t lpair_stride, size_t lstride,
+                                      const uint8_t *right, size_t rpair_stride, size_t rstride, int batch, int rows, int cols,
+                                      int window_rad, int min_disparity, int max_disparity, int flags, int8_t *disp,
+                                      size_t dpair_stride, size_t dstride, micv_stream stream);
 /* cuda::disparityNCorr, ps2_cpp/lib/DisparityNCorr.cu:177-251 (a13). */
 int micv_disparity_ncorr_dev(micv_ctx *ctx, const float *left, const float *right, int rows,
                              int cols, size_t stride, int window_rad, int min_disparity,

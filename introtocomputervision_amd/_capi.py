@@ -147,6 +147,9 @@ SIGNATURES = {
     "micv_disparity_ssd_u8_dev": (i32, [vp, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     "micv_disparity_ssd_u8_host": (i32, [vp, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, vp, sz]),
     "micv_disparity_ssd_u8_batch_dev": (i32, [vp, vp, sz, sz, vp, sz, sz, i32, i32, i32, i32, i32, i32, i32, vp, sz, sz, vp]),
+    "micv_disparity_ncorr_u8_dev": (i32, [vp, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "micv_disparity_ncorr_u8_host": (i32, [vp, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, vp, sz]),
+    "micv_disparity_ncorr_u8_batch_dev": (i32, [vp, vp, sz, sz, vp, sz, sz, i32, i32, i32, i32, i32, i32, i32, vp, sz, sz, vp]),
     "micv_disparity_ncorr_dev": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, vp, sz, vp]),
     "micv_disparity_ncorr_host": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, vp, sz]),
     # ps1

@@ -521,23 +521,37 @@ int micv_disparity_ncorr_host(micv_ctx *ctx, const float *left, const float *rig
                        max_disparity, flags, disp, dstride);
 }
 
-// 1 B per pixel and image up, where the f32 entry sends 4
-int micv_disparity_ssd_u8_host(micv_ctx *ctx, const uint8_t *left, size_t lstride, const uint8_t *right, size_t rstride,
-                               int rows, int cols, int window_rad, int min_disparity, int max_disparity, int flags,
-                               int8_t *disp, size_t dstride) {
-    HostCall h(ctx, "micv_disparity_ssd_u8_host");
+// 1 B per pixel and image up, where the f32 entries send 4
+static int stereo_u8_host(bool ncc, const char *fn, micv_ctx *ctx, const uint8_t *left, size_t lstride, const uint8_t *right,
+                          size_t rstride, int rows, int cols, int rad, int min_d, int max_d, int flags, int8_t *disp, size_t dstride) {
+    HostCall h(ctx, fn);
     if (!h.ok()) return h.finish();
-    MICV_REQUIRE(left && right && disp && rows > 0 && cols > 0, "micv_disparity_ssd_u8_host: null argument or bad size");
-    MICV_REQUIRE(lstride >= (size_t)cols && rstride >= (size_t)cols && dstride >= (size_t)cols,
-                 "micv_disparity_ssd_u8_host: bad stride");
+    MICV_REQUIRE(left && right && disp && rows > 0 && cols > 0, "%s: null argument or bad size", fn);
+    MICV_REQUIRE(lstride >= (size_t)cols && rstride >= (size_t)cols && dstride >= (size_t)cols, "%s: bad stride", fn);
     const size_t rb = (size_t)cols;
     uint8_t *dl = h.up<uint8_t>(left, lstride, rb, rows), *dr = h.up<uint8_t>(right, rstride, rb, rows);
     int8_t *dd = h.alloc<int8_t>(rb * rows);
     if (!h.ok()) return h.finish();
-    MICV_TIMED(h, "disparitySSDKernel", micv_disparity_ssd_u8_dev(ctx, dl, rb, dr, rb, rows, cols, window_rad, min_disparity,
-                                                                  max_disparity, flags, dd, rb, h.s));
+    if (ncc)
+        MICV_TIMED(h, "disparityNCorrKernel",
+                   micv_disparity_ncorr_u8_dev(ctx, dl, rb, dr, rb, rows, cols, rad, min_d, max_d, flags, dd, rb, h.s));
+    else
+        MICV_TIMED(h, "disparitySSDKernel",
+                   micv_disparity_ssd_u8_dev(ctx, dl, rb, dr, rb, rows, cols, rad, min_d, max_d, flags, dd, rb, h.s));
     h.down(disp, dstride, dd, rb, rows);
     return h.finish();
+}
+int micv_disparity_ssd_u8_host(micv_ctx *ctx, const uint8_t *left, size_t lstride, const uint8_t *right, size_t rstride,
+                               int rows, int cols, int window_rad, int min_disparity, int max_disparity, int flags,
+                               int8_t *disp, size_t dstride) {
+    return stereo_u8_host(false, "micv_disparity_ssd_u8_host", ctx, left, lstride, right, rstride, rows, cols, window_rad,
+                          min_disparity, max_disparity, flags, disp, dstride);
+}
+int micv_disparity_ncorr_u8_host(micv_ctx *ctx, const uint8_t *left, size_t lstride, const uint8_t *right, size_t rstride,
+                                 int rows, int cols, int window_rad, int min_disparity, int max_disparity, int flags,
+                                 int8_t *disp, size_t dstride) {
+    return stereo_u8_host(true, "micv_disparity_ncorr_u8_host", ctx, left, lstride, right, rstride, rows, cols, window_rad,
+                          min_disparity, max_disparity, flags, disp, dstride);
 }
 
 int micv_hough_lines_host(micv_ctx *ctx, const uint8_t *mask, int rows, int cols, size_t mstride,

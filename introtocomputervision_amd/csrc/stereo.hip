@@ -31,39 +31,6 @@
 
 namespace micv {
 
-// NCC: the energy of the right-image window depends on (row, last window column) only, not on the
-// pair (x, d) that selects it, so it is summed once per position here -- same terms, same order as
-// the search loop would (column sums top -> bottom from +0, then the systolic left -> right chain) --
-// instead of once per (pixel, disparity).  One wave = 64 consecutive positions x RPW rows; the first
-// 2R lanes only feed the chain.
-template <int R, int RPW>
-__global__ __launch_bounds__(256) void stereo_energy_kernel(StereoArgs a, float *__restrict__ E) {
-    constexpr int W = 2 * R + 1, STEPS = RPW + 2 * R, OUTW = 64 - 2 * R;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ys = blockIdx.y * (4 * RPW) + wave * RPW;
-    if (ys >= a.rows || a.skip()) return;
-    const bool full = a.wcols == W;
-    const int sp = a.s_lo - 2 * R + blockIdx.x * OUTW + lane;  // position of this lane's column
-    const int xr = clampi(sp, 0, a.cols - 1);
-    float ringB[W], rvs[STEPS];
-#pragma unroll
-    for (int s = 0; s < STEPS; s++)  // every row's load first: between the stores below they waited one by one
-        rvs[s] = a.right[(size_t)clampi(ys - R + s, 0, a.rows - 1) * a.stride + xr];
-#pragma unroll
-    for (int s = 0; s < STEPS; s++) {
-        const float rv = rvs[s];
-        ringB[s % W] = rv * rv;
-        if (s >= 2 * R) {
-            float csb = 0.f;
-#pragma unroll
-            for (int k = 0; k < W; k++) csb += ringB[(s - 2 * R + k) % W];
-            const float accb = systolic_sum<W>(csb, full);
-            const int y = ys + s - 2 * R, e = sp - a.s_lo;
-            if (lane >= 2 * R && y < a.rows && e < a.e_width) E[(size_t)y * a.e_width + e] = accb;
-        }
-    }
-}
-
 template <int R, int MODE, int RPW, int ST_DCH = ST_DCH_DEFAULT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == ST_NCC ? 1 : 3, MODE == ST_NCC ? 8 : 3)))
 void stereo_kernel(StereoArgs a) {
@@ -199,20 +166,13 @@ __global__ __launch_bounds__(256) void stereo_generic_kernel(StereoArgs a, int r
     a.disp[(size_t)y * a.dstride + x] = (int8_t)bestd;
 }
 
-// NCC's chunk of disparities: 64 (r05).  r03 chose 32 to keep 3-4 workgroups per CU beside the staged energy rows; with the
-// prefetched strips the kernel runs two waves per SIMD whatever the chunk, and half as many stagings win: 0.326 -> 0.316 ms at C3.
-#ifndef MICV_NCC_DCH
-#define MICV_NCC_DCH 64
-#endif
 template <int MODE>
 static int launch_stereo(hipStream_t s, const StereoArgs &a, int r, int force_rpw) {
     const bool ten = stereo_rows10(a.rows, a.cols, r, force_rpw);
 #define MICV_ST_LAUNCH(RR, RPW)                                                                    \
     do {                                                                                           \
         if (MODE == ST_NCC) {                                                                      \
-            /*  the staged strips of a 64-disparity chunk pass 64 KB of dynamic LDS for 2 RPW + 2 R > 32 */ \
-            /* (radius 9, 10; radius 7, 8 at 10 rows): those instantiations keep the 32-disparity chunk */          \
-            constexpr int DCH = (2 * RPW + 2 * RR) * (64 + MICV_NCC_DCH) * 16 > 65536 ? 32 : MICV_NCC_DCH;           \
+            constexpr int DCH = stereo_ncc_dch(RR, RPW);                                           \
             stereo_energy_kernel<RR, RPW><<<dim3(cdiv(a.e_width, 64 - 2 * RR), cdiv(a.rows, 4 * RPW)), 256, 0, s>>>( \
                 a, const_cast<float *>(a.energy));                                                 \
             stereo_kernel<RR, MODE, RPW, DCH><<<dim3(cdiv(a.cols, 64 - 2 * RR), cdiv(a.rows, 4 * RPW)), 256, \
@@ -258,6 +218,16 @@ static int stereo_check(const char *fn, const void *ctx, const void *left, const
     return MICV_OK;
 }
 
+// NCC's tile forms (stereo_tile<R, ST_NCC>) and the window-energy field they read: the positions a window's last column can
+// take -- lanes reach from -R to past cols + R (whole 64-lane strips), shifted by every disparity.  -> bytes of one plane.
+static bool stereo_ncc_tiled(int rad, int flags) { return rad >= 1 && rad <= 10 && !(flags & MICV_STEREO_ROLLING); }
+static size_t stereo_energy_field(int rows, int cols, int rad, int min_d, int max_d, int *s_lo, int *e_width) {
+    const int outw = 64 - 2 * rad;
+    *s_lo = -rad + min_d;
+    *e_width = (int)cdiv(cols, outw) * outw + 64 + (max_d - min_d);
+    return Carver::need((size_t)rows * *e_width, 4);
+}
+
 static int stereo_common(const char *fn, micv_ctx *ctx, const float *left, const float *right,
                          int rows, int cols, size_t stride, int rad, int min_d, int max_d,
                          int flags, int8_t *disp, size_t dstride, micv_stream stream, bool ncc) {
@@ -273,14 +243,7 @@ static int stereo_common(const char *fn, micv_ctx *ctx, const float *left, const
     a.energy = nullptr; a.e_width = 0; a.s_lo = 0;
     a.fallback_flag = nullptr; a.epoch = 0;
     size_t energy_bytes = 0;
-    if (ncc && rad >= 1 && rad <= 10 && !(flags & MICV_STEREO_ROLLING)) {
-        // positions a window's last column can take: lanes reach from -R to past cols + R (whole
-        // 64-lane strips), shifted by every disparity
-        const int outw = 64 - 2 * rad;
-        a.s_lo = -rad + min_d;
-        a.e_width = (int)cdiv(cols, outw) * outw + 64 + (max_d - min_d);
-        energy_bytes = Carver::need((size_t)rows * a.e_width, 4);
-    }
+    if (ncc && stereo_ncc_tiled(rad, flags)) energy_bytes = stereo_energy_field(rows, cols, rad, min_d, max_d, &a.s_lo, &a.e_width);
     // 8-bit-valued images (every plain ps2 call, main.cpp:87-88): the exact-sum kernels go first and the kernels below
     // return at once unless the pack pre-pass found a pixel that is not an integer in 0..255 (no host round trip).
     const bool exact = ctx->opt[MICV_OPT_STEREO_EXACT] >= 0 && stereo_exact_covers(rad, flags, ncc);
@@ -313,8 +276,9 @@ static int stereo_common(const char *fn, micv_ctx *ctx, const float *left, const
     return launch_stereo<ST_SSD>(s, a, rad, rpw);
 }
 
-// ---- disparitySSD on byte images (the u8 entries) -----------------------------------------------------------------------
-// Two byte images -> two dense f32 images, for the forms the exact-sum kernels do not cover.
+// ---- disparitySSD / disparityNCorr on byte images (the u8 entries) -------------------------------------------------------
+// Two byte images -> two dense f32 images, for the forms that neither the exact-sum kernels (SSD) nor the byte-reading
+// tiles (NCC) cover.
 __global__ __launch_bounds__(256) void stereo_u8_to_f32_kernel(const uint8_t *left, size_t lstride, const uint8_t *right,
                                                                size_t rstride, int rows, int cols, float *out) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -327,20 +291,48 @@ constexpr size_t kStereoU8BatchBytes = size_t(64) << 20;  // mi_cv.h: MICV_OPT_S
 
 static int stereo_u8_common(const char *fn, micv_ctx *ctx, const uint8_t *left, size_t lpair, size_t lstride,
                             const uint8_t *right, size_t rpair, size_t rstride, int batch, int rows, int cols, int rad,
-                            int min_d, int max_d, int flags, int8_t *disp, size_t dpair, size_t dstride, micv_stream stream) {
+                            int min_d, int max_d, int flags, int8_t *disp, size_t dpair, size_t dstride, micv_stream stream,
+                            bool ncc) {
     const size_t lim = (size_t)1 << 30;
     MICV_TRY(stereo_check(fn, ctx, left, right, rows, cols, rad, min_d, max_d, flags, disp,
                           rows > 0 && cols > 0 && lstride >= (size_t)cols && rstride >= (size_t)cols && dstride >= (size_t)cols &&
-                              lstride < lim && rstride < lim && dstride < lim, false));
+                              lstride < lim && rstride < lim && dstride < lim, ncc));
     MICV_REQUIRE(batch >= 1, "%s: batch %d", fn, batch);
     MICV_REQUIRE(batch == 1 || dpair >= (size_t)(rows - 1) * dstride + (size_t)cols,
                  "%s: the disparity maps of a batch overlap (pair stride %zu)", fn, dpair);
     MICV_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t bound = ctx->opt[MICV_OPT_STEREO_BATCH_MB] > 0 ? (size_t)ctx->opt[MICV_OPT_STEREO_BATCH_MB] << 20 : kStereoU8BatchBytes;
+    if (ncc && stereo_ncc_tiled(rad, flags)) {
+        // disparityNCorr's tile forms read the bytes themselves (stereo_ncc_u8.hip): an energy launch and a search launch per
+        // piece, the pair a grid dimension, one f32 energy plane per pair in the arena and no f32 image anywhere.  A piece is
+        // as many pairs as keep the planes within the bound -- one at least, 65535 (grid.z) at most.
+        StereoArgs8 a;
+        a.lstride = (int)lstride; a.rstride = (int)rstride;
+        a.rows = rows; a.cols = cols; a.min_d = min_d; a.max_d = max_d;
+        a.wcols = (flags & MICV_STEREO_COLS_2R) ? 2 * rad : 2 * rad + 1;
+        a.init_best = 0.f;
+        a.dstride = (int)dstride;
+        a.lpair = lpair; a.rpair = rpair; a.dpair = dpair;
+        const size_t plane = stereo_energy_field(rows, cols, rad, min_d, max_d, &a.s_lo, &a.e_width);
+        a.epair = plane / sizeof(float);
+        size_t piece = bound / plane < 1 ? 1 : bound / plane;
+        if (piece > 65535) piece = 65535;
+        if (piece > (size_t)batch) piece = batch;
+        void *scratch = nullptr;
+        MICV_TRY(ctx->reserve(piece * plane, &scratch));
+        a.energy = static_cast<float *>(scratch);
+        const bool rows10 = stereo_rows10(rows, cols, rad, ctx->opt[MICV_OPT_STEREO_ROWS]);
+        for (int i = 0; i < batch; i += (int)piece) {
+            a.left = left + i * lpair; a.right = right + i * rpair; a.disp = disp + i * dpair;
+            MICV_TRY(stereo_ncc_u8_launch(s, a, batch - i < (int)piece ? batch - i : (int)piece, rad, rows10));
+        }
+        return MICV_OK;
+    }
     // The dispatch, on the host: on bytes the rolling column sums ARE the fresh ones (integers below 2^24), so ROLLING
     // goes where the call without it goes -- radius 1..7 to the exact-sum kernels.
     const int xflags = (rad >= 1 && rad <= 7) ? flags & ~MICV_STEREO_ROLLING : flags;
-    if (ctx->opt[MICV_OPT_STEREO_EXACT] >= 0 && stereo_exact_covers(rad, xflags, false)) {
+    if (!ncc && ctx->opt[MICV_OPT_STEREO_EXACT] >= 0 && stereo_exact_covers(rad, xflags, false)) {
         const int wcols = (xflags & MICV_STEREO_COLS_2R) ? 2 * rad : 2 * rad + 1, slots = ctx->wave_slots(3);
         unsigned *flag;
         MICV_TRY(ctx->stereo_flag_word(&flag));
@@ -348,7 +340,6 @@ static int stereo_u8_common(const char *fn, micv_ctx *ctx, const uint8_t *left, 
         // than a grid has rows.  What a pair takes depends on the tiling, and the tiling on how many pairs it sees: the size
         // is asked for the piece itself, and every piece -- the shorter last one too -- is tiled as the full piece is, so the
         // one reservation holds each of them (stereo_exact_launch_u8 checks that against the bytes it is given).
-        const size_t bound = ctx->opt[MICV_OPT_STEREO_BATCH_MB] > 0 ? (size_t)ctx->opt[MICV_OPT_STEREO_BATCH_MB] << 20 : kStereoU8BatchBytes;
         auto planes = [&](size_t pairs) {
             return stereo_exact_scratch(rows, cols, rad, min_d, max_d, wcols, xflags, slots, (int)pairs, (int)pairs);
         };
@@ -382,7 +373,7 @@ static int stereo_u8_common(const char *fn, micv_ctx *ctx, const uint8_t *left, 
                                                                                       rstride, rows, cols, f);
         MICV_LAUNCH_CHECK();
         MICV_TRY(stereo_common(fn, ctx, f, f + (size_t)rows * cols, rows, cols, (size_t)cols * 4, rad, min_d, max_d, flags,
-                               disp + i * dpair, dstride, stream, false));
+                               disp + i * dpair, dstride, stream, ncc));
     }
     return MICV_OK;
 }
@@ -413,7 +404,7 @@ int micv_disparity_ssd_u8_dev(micv_ctx *ctx, const uint8_t *left, size_t lstride
                               int rows, int cols, int window_rad, int min_disparity, int max_disparity, int flags,
                               int8_t *disp, size_t dstride, micv_stream stream) {
     return stereo_u8_common("micv_disparity_ssd_u8", ctx, left, 0, lstride, right, 0, rstride, 1, rows, cols, window_rad,
-                            min_disparity, max_disparity, flags, disp, 0, dstride, stream);
+                            min_disparity, max_disparity, flags, disp, 0, dstride, stream, false);
 }
 
 int micv_disparity_ssd_u8_batch_dev(micv_ctx *ctx, const uint8_t *left, size_t lpair_stride, size_t lstride,
@@ -421,7 +412,22 @@ int micv_disparity_ssd_u8_batch_dev(micv_ctx *ctx, const uint8_t *left, size_t l
                                     int window_rad, int min_disparity, int max_disparity, int flags, int8_t *disp,
                                     size_t dpair_stride, size_t dstride, micv_stream stream) {
     return stereo_u8_common("micv_disparity_ssd_u8_batch", ctx, left, lpair_stride, lstride, right, rpair_stride, rstride, batch,
-                            rows, cols, window_rad, min_disparity, max_disparity, flags, disp, dpair_stride, dstride, stream);
+                            rows, cols, window_rad, min_disparity, max_disparity, flags, disp, dpair_stride, dstride, stream, false);
+}
+
+int micv_disparity_ncorr_u8_dev(micv_ctx *ctx, const uint8_t *left, size_t lstride, const uint8_t *right, size_t rstride,
+                                int rows, int cols, int window_rad, int min_disparity, int max_disparity, int flags,
+                                int8_t *disp, size_t dstride, micv_stream stream) {
+    return stereo_u8_common("micv_disparity_ncorr_u8", ctx, left, 0, lstride, right, 0, rstride, 1, rows, cols, window_rad,
+                            min_disparity, max_disparity, flags, disp, 0, dstride, stream, true);
+}
+
+int micv_disparity_ncorr_u8_batch_dev(micv_ctx *ctx, const uint8_t *left, size_t lpair_stride, size_t lstride,
+                                      const uint8_t *right, size_t rpair_stride, size_t rstride, int batch, int rows, int cols,
+                                      int window_rad, int min_disparity, int max_disparity, int flags, int8_t *disp,
+                                      size_t dpair_stride, size_t dstride, micv_stream stream) {
+    return stereo_u8_common("micv_disparity_ncorr_u8_batch", ctx, left, lpair_stride, lstride, right, rpair_stride, rstride, batch,
+                            rows, cols, window_rad, min_disparity, max_disparity, flags, disp, dpair_stride, dstride, stream, true);
 }
 
 }  // extern "C"

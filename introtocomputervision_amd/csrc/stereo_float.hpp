@@ -1,6 +1,7 @@
 // stereo_float.hpp -- the float stereo search's tile body (SSD / serial:: / NCC on general f32 images), shared between
 // stereo.hip (its own launch) and stereo_exact.hip (the exact-sum launch carries the float tiles of the same call as
 // trailing workgroups, so that an 8-bit-valued pair costs no third launch).  See stereo.hip for the kernel's description.
+// stereo_ncc_u8.hip instantiates the NCC tile and the energy kernel on byte images (StereoArgs8).
 #pragma once
 #include <type_traits>
 
@@ -50,6 +51,48 @@ struct StereoArgs {
     __device__ bool skip() const { return fallback_flag && __builtin_nontemporal_load(fallback_flag) != epoch; }
 };
 
+// The same search on BYTE images (the u8 entries of disparityNCorr, stereo_ncc_u8.hip): each image with its own row pitch in
+// bytes, no alignment anywhere, and a launch that covers `batch` pairs of one size -- pair blockIdx.z at base + z * pair
+// stride, its window-energy plane at energy + z * epair.  A struct of its own, so that StereoArgs and every kernel that takes
+// one stay as they are; stereo_tile and stereo_energy_kernel select the byte loads at compile time.
+struct StereoArgs8 {
+    const uint8_t *left, *right;
+    int lstride, rstride;  // bytes
+    int rows, cols, min_d, max_d;
+    int wcols;
+    float init_best;
+    int8_t *disp;
+    int dstride;
+    float *energy;  // as StereoArgs::energy, one plane per pair
+    int e_width, s_lo;
+    size_t lpair, rpair, dpair, epair;  // bytes, bytes, bytes, floats
+    __device__ bool skip() const { return false; }
+    __device__ void select(unsigned pair) {
+        left += pair * lpair;
+        right += pair * rpair;
+        disp += pair * dpair;
+        energy += pair * epair;
+    }
+};
+
+// Pixel (y, x) of an image as the search's f32 operand: bytes are converted where they are staged.
+template <typename A>
+constexpr bool st_u8 = std::is_same<A, StereoArgs8>::value;
+template <typename A>
+__device__ __forceinline__ float st_left(const A &a, int y, int x) {
+    if constexpr (st_u8<A>) return (float)a.left[(size_t)y * a.lstride + x];
+    else return a.left[(size_t)y * a.stride + x];
+}
+// (`right` as it is loaded: the prefetch registers of a byte image hold the raw byte, zero-extended -- a byte load fills a
+// VGPR whether it is converted or not, and a conversion written at the load would wait for it in front of the search loop
+// the prefetch is there to hide it under; v_cvt_f32_ubyte0 runs at the staging instead, where NccRange's four
+// instructions per value are no longer needed)
+template <typename A>
+__device__ __forceinline__ auto st_right_raw(const A &a, int y, int x) {
+    if constexpr (st_u8<A>) return (unsigned)a.right[(size_t)y * a.rstride + x];
+    else return a.right[(size_t)y * a.stride + x];
+}
+
 // Rows per wave of the float search: 8, or 10 when that lets the whole grid be resident at once (4 waves/SIMD on
 // 256 CUs = 4096 wave slots; 1080p r=5: 3888 waves instead of 4860 = one round, no tail).
 inline bool stereo_rows10(int rows, int cols, int r, int force_rpw) {
@@ -60,18 +103,30 @@ inline bool stereo_rows10(int rows, int cols, int r, int force_rpw) {
 
 // LDS budget of the staged right-image strip: DCH disparities per chunk -> SPAN columns per row.
 constexpr int ST_DCH_DEFAULT = 64;
+// NCC's chunk of disparities: 64 (r05).  r03 chose 32 to keep 3-4 workgroups per CU beside the staged energy rows; with the
+// prefetched strips the kernel runs two waves per SIMD whatever the chunk, and half as many stagings win: 0.326 -> 0.316 ms at C3.
+#ifndef MICV_NCC_DCH
+#define MICV_NCC_DCH 64
+#endif
+//  the staged strips of a 64-disparity chunk pass 64 KB of dynamic LDS for 2 RPW + 2 R > 32 (radius 9, 10;
+// radius 7, 8 at 10 rows): those instantiations keep the 32-disparity chunk
+constexpr int stereo_ncc_dch(int r, int rpw) { return (2 * rpw + 2 * r) * (64 + MICV_NCC_DCH) * 16 > 65536 ? 32 : MICV_NCC_DCH; }
 
 #ifndef MICV_STEREO_PF
 #define MICV_STEREO_PF 2
 #endif
 
-template <int R, int MODE, int RPW, int ST_DCH>
+template <int R, int MODE, int RPW, int ST_DCH, typename A = StereoArgs>
 // Register budget: LDS allows three workgroups per CU = three waves per SIMD, so the SSD forms may take 170 VGPRs instead
 // of the 128 the default heuristic aims at (r05 A/B on one box: 0.2246-0.2267 -> 0.2176-0.2208 ms at C3); NCC with its
 // prefetched strips keeps the default budget -- it then takes 243 VGPRs = two waves per SIMD, 0.326 ms; capped at 170 it spills
 // (0.389 ms), told "two waves" it allocates 179 and schedules worse (0.417 ms).
-__device__ __forceinline__ void stereo_tile(const StereoArgs &a, float *st_lds, const int bx, const int by) {
+__device__ __forceinline__ void stereo_tile(const A &a, float *st_lds, const int bx, const int by) {
     constexpr int W = 2 * R + 1, STEPS = RPW + 2 * R, OUTW = 64 - 2 * R, ST_SPAN = 64 + ST_DCH;
+    // byte images (NCC only): a byte is 0 or in [1, 255], a window energy 0 or in [1, 255^2 * 21^2] < 2^39 -- every operand is
+    // in the range of the short arithmetic, known here and not tracked
+    constexpr bool U8 = st_u8<A>;
+    static_assert(!U8 || MODE == ST_NCC, "the byte source serves NCC; SSD on bytes is stereo_exact.hip's");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // scalar row addressing
     const bool full = a.wcols == W;
@@ -92,12 +147,12 @@ __device__ __forceinline__ void stereo_tile(const StereoArgs &a, float *st_lds, 
 #pragma unroll
     for (int s = 0; s < STEPS; s++) {
         const int yy = clampi(ys - R + s, 0, a.rows - 1);
-        Lv[s] = a.left[(size_t)yy * a.stride + xl];
+        Lv[s] = st_left(a, yy, xl);
     }
 
     // NCC: operands in the checked range take the short exact sqrt / division (ncc_arith.hpp)
     NccRange pix_l;
-    if (MODE == ST_NCC) {
+    if (MODE == ST_NCC && !U8) {
 #pragma unroll
         for (int s = 0; s < STEPS; s++) pix_l.add(Lv[s]);
     }
@@ -138,10 +193,11 @@ __device__ __forceinline__ void stereo_tile(const StereoArgs &a, float *st_lds, 
     constexpr int PF = MODE == ST_NCC ? MICV_STEREO_PF : 0;  // 0 = no prefetch, 1 = the right strip, 2 = + the energy strip
     static_assert(MODE != ST_NCC || PF == 2, "the NCC staging below reads the prefetched energy strip (pre_e)");
     constexpr int NH = (ST_SPAN + 63) / 64;
-    float pre_r[PF >= 1 ? STEPS : 1][NH], pre_e[PF >= 2 && ESTEPS > 0 ? ESTEPS : 1][NH];
+    decltype(st_right_raw(a, 0, 0)) pre_r[PF >= 1 ? STEPS : 1][NH];
+    float pre_e[PF >= 2 && ESTEPS > 0 ? ESTEPS : 1][NH];
     auto load_r = [&](int d0, int s, int h) {
         const int yy = clampi(ys - R + s, 0, a.rows - 1), i = lane + 64 * h;
-        return a.right[(size_t)yy * a.stride + clampi(x_base + d0 + (i < ST_SPAN ? i : ST_SPAN - 1), 0, a.cols - 1)];
+        return st_right_raw(a, yy, clampi(x_base + d0 + (i < ST_SPAN ? i : ST_SPAN - 1), 0, a.cols - 1));
     };
     auto load_e = [&](int d0, int j, int h) {
         const int i = lane + 64 * h;
@@ -175,9 +231,9 @@ __device__ __forceinline__ void stereo_tile(const StereoArgs &a, float *st_lds, 
             for (int h = 0; h < NH; h++) {
                 const int i = lane + 64 * h;
                 if (ST_SPAN % 64 == 0 || i < ST_SPAN) {
-                    const float v = PF >= 1 ? pre_r[PF >= 1 ? s : 0][h] : load_r(d0, s, h);
+                    const float v = PF >= 1 ? (float)pre_r[PF >= 1 ? s : 0][h] : (float)load_r(d0, s, h);
                     Rs[s * ST_SPAN + i] = v;
-                    if (MODE == ST_NCC) pix.add(v);
+                    if (MODE == ST_NCC && !U8) pix.add(v);
                 }
             }
         }
@@ -190,7 +246,7 @@ __device__ __forceinline__ void stereo_tile(const StereoArgs &a, float *st_lds, 
                     if (ST_SPAN % 64 == 0 || i < ST_SPAN) {
                         const float v = pre_e[j][h];
                         Es[j * ST_SPAN + i] = v;
-                        en.add(v);
+                        if (!U8) en.add(v);
                     }
                 }
             }
@@ -294,7 +350,9 @@ __device__ __forceinline__ void stereo_tile(const StereoArgs &a, float *st_lds, 
             else
                 search(short_arith, std::false_type{});
         };
-        if constexpr (MODE == ST_NCC) {
+        if constexpr (MODE == ST_NCC && U8) {
+            search_w(std::true_type{});
+        } else if constexpr (MODE == ST_NCC) {
             // wave-uniform: every staged operand of this chunk is in the checked range
             if (__builtin_amdgcn_ballot_w64(!(pix.inside(NCC_PIX_LO, NCC_PIX_HI) && en.inside(NCC_EN_LO, NCC_EN_HI))) == 0)
                 search_w(std::true_type{});
@@ -310,5 +368,48 @@ __device__ __forceinline__ void stereo_tile(const StereoArgs &a, float *st_lds, 
             if (ys + j < a.rows) a.disp[(size_t)(ys + j) * a.dstride + xo] = (int8_t)bestd[j];
     }
 }
+
+// NCC: the energy of the right-image window depends on (row, last window column) only, not on the
+// pair (x, d) that selects it, so it is summed once per position here -- same terms, same order as
+// the search loop would (column sums top -> bottom from +0, then the systolic left -> right chain) --
+// instead of once per (pixel, disparity).  One wave = 64 consecutive positions x RPW rows; the first
+// 2R lanes only feed the chain.
+// (A kernel template and not a tile body under two kernels: inlined as a function the f32 instantiations came out with other
+// registers and code than they had.  On bytes the pair is blockIdx.z and E the pair's own plane.)
+template <int R, int RPW, typename A = StereoArgs>
+__global__ __launch_bounds__(256) void stereo_energy_kernel(A a, float *__restrict__ E) {
+    if constexpr (st_u8<A>) {
+        a.select(blockIdx.z);
+        E = a.energy;
+    }
+    constexpr int W = 2 * R + 1, STEPS = RPW + 2 * R, OUTW = 64 - 2 * R;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ys = blockIdx.y * (4 * RPW) + wave * RPW;
+    if (ys >= a.rows || a.skip()) return;
+    const bool full = a.wcols == W;
+    const int sp = a.s_lo - 2 * R + blockIdx.x * OUTW + lane;  // position of this lane's column
+    const int xr = clampi(sp, 0, a.cols - 1);
+    float ringB[W], rvs[STEPS];
+#pragma unroll
+    for (int s = 0; s < STEPS; s++)  // every row's load first: between the stores below they waited one by one
+        rvs[s] = (float)st_right_raw(a, clampi(ys - R + s, 0, a.rows - 1), xr);
+#pragma unroll
+    for (int s = 0; s < STEPS; s++) {
+        const float rv = rvs[s];
+        ringB[s % W] = rv * rv;
+        if (s >= 2 * R) {
+            float csb = 0.f;
+#pragma unroll
+            for (int k = 0; k < W; k++) csb += ringB[(s - 2 * R + k) % W];
+            const float accb = systolic_sum<W>(csb, full);
+            const int y = ys + s - 2 * R, e = sp - a.s_lo;
+            if (lane >= 2 * R && y < a.rows && e < a.e_width) E[(size_t)y * a.e_width + e] = accb;
+        }
+    }
+}
+
+// stereo_ncc_u8.hip: the energy launch and the search launch of `batch` byte pairs (radius 1..10, no ROLLING), pair z of
+// the grid as StereoArgs8::select(z) places it; 8 or 10 rows per wave as stereo_rows10 says.
+int stereo_ncc_u8_launch(hipStream_t s, const StereoArgs8 &a, int batch, int rad, bool rows10);
 
 }  // namespace micv

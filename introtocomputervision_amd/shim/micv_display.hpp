@@ -119,6 +119,31 @@ inline void disparityNCorrPair(const Mat &left, const Mat &right, const bool use
     pair(true, left, right, useGpuDisparity, config, leftDisparity, rightDisparity);
 }
 
+// disparityNCorr on the 8-bit Mats main.cpp loads, without its convertTo(CV_32FC1) (main.cpp:227-229, 304-306): CV_8UC1,
+// ROI views included, each with its own step; the disparities are those of cuda:: / serial::disparityNCorr on the converted
+// pair.  (Functions of their own: cuda:: / serial::disparityNCorr and disparityNCorrPair keep refusing 8-bit Mats.)
+inline void disparityNCorr8(const Mat &left, const Mat &right, const size_t windowRad, const int minDisparity,
+                            const int maxDisparity, const bool useGpuDisparity, Mat &disparity) {
+    micv_shim::require(left.type() == micv_shim::U8 && right.type() == micv_shim::U8 && left.rows == right.rows &&
+                           left.cols == right.cols, "disparityNCorr8: CV_8UC1 pair of equal size expected");
+    Mat d;
+    d.create(left.rows, left.cols, micv_shim::S8);
+    micv_shim::check(micv_disparity_ncorr_u8_host(micv_shim::context(), left.ptr<uint8_t>(), left.step, right.ptr<uint8_t>(),
+                                                  right.step, left.rows, left.cols, static_cast<int>(windowRad), minDisparity,
+                                                  maxDisparity, stereo_flags(true, useGpuDisparity), d.ptr<int8_t>(), d.step));
+    disparity = d;
+}
+// main.cpp:51-78: the left image as reference over [-range, 0], the right one over [0, range]
+inline void disparityNCorrPair8(const Mat &left, const Mat &right, const bool useGpuDisparity, const DisparityConfig &config,
+                                Mat &leftDisparity, Mat &rightDisparity) {
+    const int range = (int)config._disparityRange;
+    Mat l, r;
+    disparityNCorr8(left, right, config._windowRadius, -range, 0, useGpuDisparity, l);
+    disparityNCorr8(right, left, config._windowRadius, 0, range, useGpuDisparity, r);
+    leftDisparity = l;
+    rightDisparity = r;
+}
+
 // The two cv::randn calls of addNoise, in its order: what pairAndDisplay takes as noise.
 inline void drawNoise(const Mat &first, const Mat &second, const float mean, const float sigma, Mat &firstNoise, Mat &secondNoise) {
     firstNoise.create(first.rows, first.cols, micv_shim::F32);

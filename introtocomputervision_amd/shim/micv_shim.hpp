@@ -581,7 +581,8 @@ inline void disparity(bool ncc, const Mat &left, const Mat &right, const size_t 
     // The 8-bit images main.cpp loads, without its convertTo(CV_32FC1) (main.cpp:87-88): SSD takes them as they are, each
     // with its own step (an ROI starts at any byte); the disparities are those of the converted pair.
     if (left.type() == U8 || right.type() == U8) {
-        require(!ncc, "disparityNCorr: CV_32FC1 images expected (8-bit pairs are taken by disparitySSD only)");
+        require(!ncc, "disparityNCorr: CV_32FC1 images expected (8-bit pairs are taken by disparitySSD, and by "
+                      "ps2::disparityNCorr8 / ps2::disparityNCorrPair8 of micv_display.hpp)");
         require(left.type() == U8 && right.type() == U8 && left.rows == right.rows && left.cols == right.cols,
                 "disparitySSD: CV_8UC1 pair of equal size expected");
         disparity.create(left.rows, left.cols, S8);

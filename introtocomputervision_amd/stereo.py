@@ -48,10 +48,7 @@ def _pitch(a):
     return a.stride(-2) if B.is_dev(a) else a.strides[-2]
 
 
-def disparitySSD8(left, right, windowRad, minDisparity, maxDisparity, flags=0, ctx=None):
-    """disparitySSD on the 8-bit images themselves (no convertTo(CV_32F)): uint8 numpy arrays take the `_host` entry, uint8
-    torch device tensors the `_dev` one; each image with its own row stride, at any byte alignment.  -> int8 disparity,
-    the bytes disparitySSD gives on the images converted to float32."""
+def _run8(dev_fn, host_fn, left, right, windowRad, minDisparity, maxDisparity, flags, ctx):
     B.check2d(left, np.uint8, name="left")
     B.check2d(right, np.uint8, name="right")
     if B.is_dev(left) != B.is_dev(right) or tuple(left.shape) != tuple(right.shape):
@@ -61,15 +58,13 @@ def disparitySSD8(left, right, windowRad, minDisparity, maxDisparity, flags=0, c
     args = (_ctx_for(left, ctx).handle, B.ptr(left), _pitch(left), B.ptr(right), _pitch(right), rows, cols, int(windowRad),
             int(minDisparity), int(maxDisparity), int(flags), B.ptr(disp), cols)
     if B.is_dev(left):
-        check(lib.micv_disparity_ssd_u8_dev(*args, B.stream_of(left)))
+        check(dev_fn(*args, B.stream_of(left)))
     else:
-        check(lib.micv_disparity_ssd_u8_host(*args))
+        check(host_fn(*args))
     return disp
 
 
-def disparitySSD8Batch(left, right, windowRad, minDisparity, maxDisparity, flags=0, ctx=None):
-    """disparitySSD8 on [batch, rows, cols] uint8 device tensors of any pair and row stride, as one pre-pass and one search
-    launch over all pairs -> [batch, rows, cols] int8; element i holds the bytes of disparitySSD8(left[i], right[i], ...)."""
+def _run8_batch(batch_fn, left, right, windowRad, minDisparity, maxDisparity, flags, ctx):
     for name, a in (("left", left), ("right", right)):
         if not B.is_dev(a) or not a.is_cuda or a.dim() != 3 or a.dtype != B.torch.uint8 or a.stride(2) != 1:
             raise ValueError(f"{name}: need a [batch, rows, cols] uint8 device tensor with unit column stride")
@@ -77,11 +72,40 @@ def disparitySSD8Batch(left, right, windowRad, minDisparity, maxDisparity, flags
         raise ValueError("left and right differ in size, or the batch is empty")
     batch, rows, cols = left.shape
     disp = B.empty_like_shape(left, (batch, rows, cols), np.int8)
-    check(lib.micv_disparity_ssd_u8_batch_dev(
+    check(batch_fn(
         _ctx_for(left, ctx).handle, B.ptr(left), left.stride(0) if batch > 1 else 0, _pitch(left), B.ptr(right),
         right.stride(0) if batch > 1 else 0, _pitch(right), batch, rows, cols, int(windowRad), int(minDisparity),
         int(maxDisparity), int(flags), B.ptr(disp), rows * cols, cols, B.stream_of(left)))
     return disp
+
+
+def disparitySSD8(left, right, windowRad, minDisparity, maxDisparity, flags=0, ctx=None):
+    """disparitySSD on the 8-bit images themselves (no convertTo(CV_32F)): uint8 numpy arrays take the `_host` entry, uint8
+    torch device tensors the `_dev` one; each image with its own row stride, at any byte alignment.  -> int8 disparity,
+    the bytes disparitySSD gives on the images converted to float32."""
+    return _run8(lib.micv_disparity_ssd_u8_dev, lib.micv_disparity_ssd_u8_host, left, right, windowRad, minDisparity,
+                 maxDisparity, flags, ctx)
+
+
+def disparitySSD8Batch(left, right, windowRad, minDisparity, maxDisparity, flags=0, ctx=None):
+    """disparitySSD8 on [batch, rows, cols] uint8 device tensors of any pair and row stride, as one pre-pass and one search
+    launch over all pairs -> [batch, rows, cols] int8; element i holds the bytes of disparitySSD8(left[i], right[i], ...)."""
+    return _run8_batch(lib.micv_disparity_ssd_u8_batch_dev, left, right, windowRad, minDisparity, maxDisparity, flags, ctx)
+
+
+def disparityNCorr8(left, right, windowRad, minDisparity, maxDisparity, flags=0, ctx=None):
+    """disparityNCorr on the 8-bit images themselves, as disparitySSD8 takes them: uint8 numpy arrays go to the `_host`
+    entry, uint8 torch device tensors to the `_dev` one.  -> int8 disparity, the bytes disparityNCorr gives on the images
+    converted to float32."""
+    return _run8(lib.micv_disparity_ncorr_u8_dev, lib.micv_disparity_ncorr_u8_host, left, right, windowRad, minDisparity,
+                 maxDisparity, flags, ctx)
+
+
+def disparityNCorr8Batch(left, right, windowRad, minDisparity, maxDisparity, flags=0, ctx=None):
+    """disparityNCorr8 on [batch, rows, cols] uint8 device tensors of any pair and row stride, the pair as a grid dimension
+    of one energy launch and one search launch -> [batch, rows, cols] int8; element i holds the bytes of
+    disparityNCorr8(left[i], right[i], ...)."""
+    return _run8_batch(lib.micv_disparity_ncorr_u8_batch_dev, left, right, windowRad, minDisparity, maxDisparity, flags, ctx)
 
 
 def disparityNCorr(left, right, windowRad, minDisparity, maxDisparity, flags=0, ctx=None):
