@@ -70,7 +70,8 @@ size_t micv_ctx_scratch_bytes(const micv_ctx *ctx);
 #define MICV_OPT_LK_STRIP          16 /* fused LK, window 15: the INTERIOR tiles of a level launch as vertical strips that a workgroup streams down in blocks of 16 rows, carrying the last 14 row-pass rows of the five product fields and two warped rows from block to block (lk_strip.hpp) -- no vertical halo recomputation; the border tiles of the same launch stay tiles: 0 = off (default: 15 % fewer instructions, the same time -- DESIGN.md section 5), n > 0 = on with row segments of n blocks (16 = 256 rows); + 8192 = only for launches of 4096 tiles or more */
 #define MICV_OPT_STEREO_EXACT      17 /* disparitySSD on 8-bit-valued images (integers 0..255 in both f32 images, radius <= 7; serial:: semantics radius <= 5): 0 = the exact-sum kernels (stereo_exact.hip: integer dot products, sliding window sums, lanes = disparities), chosen on the device per call by a pre-pass that tests every pixel (default); -1 = always the float kernels that add every window in the contract's order.  Same disparities either way: all sums are integers below 2^24, exact in f32 in any order.  (disparityNCorr always takes the float kernels; its u8 entries, micv_disparity_ncorr_u8_*, take the byte-reading float kernels of stereo_ncc_u8.hip.) */
 #define MICV_OPT_STEREO_BATCH_MB   18 /* micv_disparity_ssd_u8_batch_dev: MiB of packed planes one launch may hold before the batch is processed in pieces: 0 = 64 (default), n = 1..4096; micv_disparity_ncorr_u8_batch_dev: the same bound on a launch's f32 window-energy planes (NCC, radius 1..10 without ROLLING) */
-#define MICV_OPT_COUNT            19
+#define MICV_OPT_HARRIS_BATCH_MB   19 /* micv_harris_corners_u8_batch_dev: MiB of scratch (R planes the caller does not keep, mask words) one launch may hold before the batch is processed in pieces: 0 = 64 (default), n = 1..4096 */
+#define MICV_OPT_COUNT            20
 int micv_ctx_set_option(micv_ctx *ctx, int option, int value);
 int micv_ctx_get_option(const micv_ctx *ctx, int option, int *value);
 
@@ -389,6 +390,62 @@ int micv_harris_corners_host(micv_ctx *ctx, const float *img, int rows, int cols
                              double sigma, float alpha, int flags, double threshold, int min_distance, float *gx, float *gy,
                              size_t gstride, float *resp, size_t rstride, float *corners, size_t cstride, int32_t *locs_yx,
                              int64_t cap, int64_t *count);
+
+/* The same chain on 8-BIT images: what every ps4 call of the reference starts from (Solution::harrisHelper,
+ * ps4_cpp/src/Solution.cpp:73-74, convertTo(CV_32F)s its picture only because harris::getGradients wants floats).
+ * The arguments of micv_harris_corners_dev, with `img` bytes at a pitch of `stride` bytes (>= cols) and, before the
+ * stream, kp_size / kp_xysa: the keypoints of sift::getKeypoints at the listed corners.
+ *
+ * Contract.  For every argument set micv_harris_corners_dev accepts (any Sobel size it accepts, any odd window <= 63,
+ * MICV_HARRIS_CPU, any threshold including <= 0 and -inf, min_distance >= 0, cap below, at and above the count), every
+ * requested output -- gx, gy, resp, corners, the first min(count, cap) rows of locs_yx, count -- is byte-identical to that
+ * entry on the image converted to f32.  Batch element i is byte-identical to the single call on image i.
+ * Keypoints: with kp_xysa non-NULL, its first min(count, cap) rows ([x, y, size, angle]) are byte-identical to
+ * micv_sift_keypoints_dev(kp_size) on the f32 entry's gradient planes and list, whether or not gx / gy were requested;
+ * rows past min(count, cap) are not written.  kp_xysa == NULL: no keypoints, kp_size is ignored.  A non-NULL kp_xysa
+ * needs locs_yx.
+ * Memory: the image pointer and pitch need NO alignment; output planes keep the f32 entry's rules (strides multiples
+ * of 4, >= cols * 4).  No byte of an output plane outside rows x cols, no byte of a list outside the rows named above and
+ * no byte between a batch's planes or lists is written; no byte of the input outside the `cols` bytes of each of its
+ * `rows` rows is read (the image is read with byte loads only).  No entry synchronises the host.  batch < 1 is refused
+ * with MICV_EINVAL and a message before anything runs, and so are outputs of one batch that overlap each other: a plane's
+ * image is the (rows - 1) * stride + cols * 4 bytes from its first pixel, its image stride a multiple of 4 and at least
+ * that (planes with one image stride may interleave), and locs_yx, count and kp_xysa are dense arrays of the batch.
+ *
+ * Dispatch, decided on the host:
+ *   - 3 x 3 Sobel, window 3 / 5 / 7, neither MICV_OPT_HARRIS_GENERIC nor MICV_OPT_SOBEL_GENERIC (the fused form of
+ *     micv_harris_corners_dev): the fused response kernel reads the bytes itself and converts them as it loads them.
+ *     Device memory holds the bytes, R and what the caller asked for -- no f32 image, and no gradient plane unless
+ *     requested: on bytes every 3 x 3 Sobel value is an integer of magnitude <= 1020, the same float in any evaluation
+ *     order, so the one gradient sample a keypoint reads is recomputed at the corner from its 3 x 3 neighbourhood.
+ *   - every other form: the image is converted to f32 in the context's scratch and handed to micv_harris_corners_dev,
+ *     image by image; keypoints are then read from the gradient planes.
+ *
+ * Batch (fused form): `batch` images of one size, image i at img + i * image_stride bytes (any value), its planes at
+ * i * {g,r,c}image_stride bytes; locs_yx is [batch][cap][2], count [batch] int64, kp_xysa [batch][cap][4].  Three
+ * launches for the whole batch: the image is a grid dimension of the response launch and of the NMS launch, and the
+ * ordered lists, counts and keypoints come from one launch with ONE workgroup per image, which walks that image's
+ * rows * ceil(cols / 64) mask words in order -- no workgroup waits for another.  An image of more than 65536 such words
+ * (4 Mpx at widths that are multiples of 64) takes the list step of micv_harris_refine_dev instead, one launch per
+ * image, and one more launch for the keypoints; so does a batch of ONE image (and micv_harris_corners_u8_dev) above
+ * 8192 words, where a single workgroup would be slower than that step.  A batch that does not keep resp needs rows * cols * 4 bytes of R per
+ * image plus the mask words: past 64 MiB (MICV_OPT_HARRIS_BATCH_MB) it goes in pieces, one after the other on the
+ * stream; a piece is as many images as keep within the bound, one at least and 65535 at most.  64 x 32 response tiles
+ * are used when a launch (a piece) has 1024 of them or more, 64 x 16 otherwise; the bits do not depend on it. */
+int micv_harris_corners_u8_dev(micv_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, int sobel_ksize, int win,
+                               double sigma, float alpha, int flags, double threshold, int min_distance, float *gx, float *gy,
+                               size_t gstride, float *resp, size_t rstride, float *corners, size_t cstride, int32_t *locs_yx,
+                               int64_t cap, int64_t *count, float kp_size, float *kp_xysa, micv_stream stream);
+/* Uploads 1 B per pixel (micv_harris_corners_host: 4). */
+int micv_harris_corners_u8_host(micv_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, int sobel_ksize, int win,
+                                double sigma, float alpha, int flags, double threshold, int min_distance, float *gx, float *gy,
+                                size_t gstride, float *resp, size_t rstride, float *corners, size_t cstride, int32_t *locs_yx,
+                                int64_t cap, int64_t *count, float kp_size, float *kp_xysa);
+int micv_harris_corners_u8_batch_dev(micv_ctx *ctx, const uint8_t *img, size_t image_stride, int batch, int rows, int cols, size_t stride,
+                                     int sobel_ksize, int win, double sigma, float alpha, int flags, double threshold, int min_distance,
+                                     float *gx, float *gy, size_t gimage_stride, size_t gstride, float *resp, size_t rimage_stride,
+                                     size_t rstride, float *corners, size_t cimage_stride, size_t cstride, int32_t *locs_yx, int64_t cap,
+                                     int64_t *count, float kp_size, float *kp_xysa, micv_stream stream);
 
 /* sift::getAnglesFromGradients, ps4_cpp/lib/Descriptors.cpp:7-25 (a11). */
 int micv_sift_angles_dev(micv_ctx *ctx, const float *gx, const float *gy, int rows, int cols,

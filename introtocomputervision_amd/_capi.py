@@ -47,7 +47,7 @@ PS4_NO_GLYPHS = 1  # ps4 driver (mi_cv.h)
 (OPT_LK_STREAM_GROUPS, OPT_LK_FORCE_GENERIC, OPT_LK_NARROW_TILES, OPT_SOBEL_GENERIC, OPT_HARRIS_GENERIC,
  OPT_NMS_SCAN, OPT_STEREO_ROWS, OPT_LK_CHAIN, OPT_LK_SHORT_TILES, OPT_LK_STREAM, OPT_LK_TALL_TILES,
  OPT_COMPACT_3PASS, OPT_LK_DIRECT_LEVELS, OPT_LK_BUILD_OVERLAP, OPT_LK_SPLIT, OPT_LK_STRIP,
- OPT_STEREO_EXACT, OPT_STEREO_BATCH_MB) = range(1, 19)
+ OPT_STEREO_EXACT, OPT_STEREO_BATCH_MB, OPT_HARRIS_BATCH_MB) = range(1, 20)
 
 
 MICV_COMM_ID_BYTES = 128  # mi_cv.h
@@ -135,6 +135,10 @@ SIGNATURES = {
     "micv_harris_refine_host": (i32, [vp, vp, i32, i32, sz, f64, i32, vp, sz, vp, i64, vp]),
     "micv_harris_corners_dev": (i32, [vp, vp, i32, i32, sz, i32, i32, f64, f32, i32, f64, i32, vp, vp, sz, vp, sz, vp, sz, vp, i64, vp, vp]),
     "micv_harris_corners_host": (i32, [vp, vp, i32, i32, sz, i32, i32, f64, f32, i32, f64, i32, vp, vp, sz, vp, sz, vp, sz, vp, i64, vp]),
+    "micv_harris_corners_u8_dev": (i32, [vp, vp, i32, i32, sz, i32, i32, f64, f32, i32, f64, i32, vp, vp, sz, vp, sz, vp, sz, vp, i64, vp, f32, vp, vp]),
+    "micv_harris_corners_u8_host": (i32, [vp, vp, i32, i32, sz, i32, i32, f64, f32, i32, f64, i32, vp, vp, sz, vp, sz, vp, sz, vp, i64, vp, f32, vp]),
+    "micv_harris_corners_u8_batch_dev": (i32, [vp, vp, sz, i32, i32, i32, sz, i32, i32, f64, f32, i32, f64, i32, vp, vp, sz, sz, vp, sz, sz, vp, sz, sz,
+                                               vp, i64, vp, f32, vp, vp]),
     "micv_sift_angles_dev": (i32, [vp, vp, vp, i32, i32, sz, vp, sz, vp]),
     "micv_sift_angles_host": (i32, [vp, vp, vp, i32, i32, sz, vp, sz]),
     "micv_sift_keypoints_dev": (i32, [vp, vp, vp, i32, i32, sz, vp, i64, f32, vp, vp]),

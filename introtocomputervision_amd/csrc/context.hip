@@ -398,6 +398,8 @@ int micv_ctx_set_option(micv_ctx *ctx, int option, int value) {
         MICV_REQUIRE(value >= -1 && value <= 0, "micv_ctx_set_option: exact-sum stereo must be 0 (automatic) or -1 (never)");
     if (option == MICV_OPT_STEREO_BATCH_MB)
         MICV_REQUIRE(value >= 0 && value <= 4096, "micv_ctx_set_option: stereo batch pieces must be 0 (64 MiB) or 1..4096 MiB");
+    if (option == MICV_OPT_HARRIS_BATCH_MB)
+        MICV_REQUIRE(value >= 0 && value <= 4096, "micv_ctx_set_option: Harris batch pieces must be 0 (64 MiB) or 1..4096 MiB");
     ctx->opt[option] = value;
     return MICV_OK;
 }

@@ -243,11 +243,29 @@ struct Sobel3 {
     float row_dx[3], col_dx[3], row_dy[3], col_dy[3];
 };
 
-template <int R, int TH, bool CPU>
-__global__ __launch_bounds__(16 * TH) void harris_image_response_kernel(const float *__restrict__ img, int istride, int rows, int cols,
+// PX = float: the image as micv_harris_corners_dev takes it, and no further argument -- the kernel of that entry, unchanged.
+// PX = uint8_t: the byte source of micv_harris_corners_u8_* (istride is then the pitch in bytes, and neither the pointer
+// nor the pitch is aligned to anything): the same jobs with each pixel loaded as a byte and converted where the float one
+// is loaded -- everything after the load is the float code.  It takes one more argument, a HarrisBatch: the image is
+// blockIdx.z.
+struct HarrisBatch {
+    size_t img, resp, grad;  // from one image to the next: bytes of the input, floats of R and of the gradient planes
+};
+template <int R, int TH, bool CPU, typename PX = float, typename... BATCH>
+__global__ __launch_bounds__(16 * TH) void harris_image_response_kernel(const PX *__restrict__ img, int istride, int rows, int cols,
                                                                          Sobel3 t, HarrisW<R> hw, float alpha, float *__restrict__ resp,
                                                                          int rstride, float *__restrict__ gxo, float *__restrict__ gyo,
-                                                                         int gstride, int vec_ok, int img_vec_ok) {
+                                                                         int gstride, int vec_ok, int img_vec_ok, BATCH... batch) {
+    if constexpr (sizeof...(BATCH) > 0) {
+        const HarrisBatch b = (batch, ...);
+        const size_t z = blockIdx.z;
+        img += z * b.img;
+        resp += z * b.resp;
+        if (gxo) {
+            gxo += z * b.grad;
+            gyo += z * b.grad;
+        }
+    }
     constexpr int TW = 64, NT = 16 * TH, RH = TH + 2 * R, PS = 80, PC = TW + 8;  // plane columns x0 - 4 .. x0 + 67
     // LDS: the three product planes and nothing else -- the same 34.5 KB (window 5, 64x32 tile) as the kernel that reads
     // gradients from HBM, i.e. the same four workgroups per CU (a staged image tile + row-pass planes took 56 KB = two
@@ -275,13 +293,17 @@ __global__ __launch_bounds__(16 * TH) void harris_image_response_kernel(const fl
         // pair's -- every load issued before the first use
         hv2f va[SEG + 2], vb[SEG + 2], vc[SEG + 2];
         if (interior) {
-            const float *sp = img + (size_t)(y0 - R + q0 - 1) * istride + (x0 - 4 + lx - 1);  // (odd column: 4-byte aligned pairs)
+            const PX *sp = img + (size_t)(y0 - R + q0 - 1) * istride + (x0 - 4 + lx - 1);  // (odd column: 4-byte aligned pairs)
 #pragma unroll
             for (int k = 0; k < SEG + 2; k++) {
-                const float *rp = sp + (size_t)k * istride;
-                const float v0 = rp[0];
-                const hv2f v12 = *reinterpret_cast<const hv2f *>(rp + 1);
-                const float v3 = rp[3];
+                const PX *rp = sp + (size_t)k * istride;
+                const float v0 = (float)rp[0];
+                hv2f v12;
+                if constexpr (sizeof(PX) == 4)
+                    v12 = *reinterpret_cast<const hv2f *>(rp + 1);
+                else  // bytes: four byte loads, all inside the row (interior: columns x0 - 5 .. x0 + 68 < cols); no wide load
+                    v12 = (hv2f){(float)rp[1], (float)rp[2]};
+                const float v3 = (float)rp[3];
                 va[k] = (hv2f){v0, v12.x};
                 vb[k] = v12;
                 vc[k] = (hv2f){v12.y, v3};
@@ -338,8 +360,9 @@ __global__ __launch_bounds__(16 * TH) void harris_image_response_kernel(const fl
                 const int ys[3] = {reflect101(cy - 1, rows), cy, reflect101(cy + 1, rows)};
 #pragma unroll
                 for (int k = 0; k < 3; k++) {
-                    const float *rp = img + (size_t)ys[k] * istride;
-                    rowpass_v((hv2f){rp[xa[0]], rp[xb[0]]}, (hv2f){rp[xa[1]], rp[xb[1]]}, (hv2f){rp[xa[2]], rp[xb[2]]}, k);
+                    const PX *rp = img + (size_t)ys[k] * istride;
+                    rowpass_v((hv2f){(float)rp[xa[0]], (float)rp[xb[0]]}, (hv2f){(float)rp[xa[1]], (float)rp[xb[1]]},
+                              (hv2f){(float)rp[xa[2]], (float)rp[xb[2]]}, k);
                 }
                 finish(q, 0, 1, 2);
             }
@@ -347,6 +370,50 @@ __global__ __launch_bounds__(16 * TH) void harris_image_response_kernel(const fl
     }
     __syncthreads();
     harris_tile_accumulate<R, TH, CPU>(XX, XY, YY, hw, alpha, resp, rstride, rows, cols, x0, y0, vec_ok);
+}
+
+static void harris_image_tables(const Taps &g, int r, float *w, Sobel3 *t) {
+    for (int wy = 0; wy <= 2 * r; wy++)
+        for (int wx = 0; wx <= 2 * r; wx++) w[wy * (2 * r + 1) + wx] = g.k[wy] * g.k[wx];
+    Taps d, m;
+    sobel_taps(3, 1, &d);
+    sobel_taps(3, 0, &m);
+    for (int i = 0; i < 3; i++) {  // filters.hip, launch_sobel_fused with scale 1 (harris::getGradients)
+        t->row_dx[i] = d.k[i];
+        t->col_dx[i] = m.k[i];
+        t->row_dy[i] = m.k[i];
+        t->col_dy[i] = d.k[i];
+    }
+}
+
+template <int R, bool CPU>
+static void launch_harris_image_u8(hipStream_t s, const HarrisU8Launch &a) {
+    HarrisW<R> hw;
+    Sobel3 t;
+    harris_image_tables(a.g, R, hw.w, &t);
+    const int rs = (int)(a.rstride / 4), gs = a.gx ? (int)(a.gstride / 4) : 0;
+    // every image's planes are aligned alike only when the distances between them keep the alignment
+    const int vec_ok = ((reinterpret_cast<uintptr_t>(a.resp) | a.resp_dist) & 15) == 0 && (rs & 3) == 0;
+    // (the byte loads need nothing; the marching body stores gradient pairs, 8 B)
+    const int img_vec_ok = !a.gx || (((reinterpret_cast<uintptr_t>(a.gx) | reinterpret_cast<uintptr_t>(a.gy) | a.grad_dist) & 7) == 0 && (gs & 1) == 0);
+    const HarrisBatch b{a.img_dist, a.resp_dist / 4, a.grad_dist / 4};
+    if (a.tall)
+        harris_image_response_kernel<R, 32, CPU, uint8_t, HarrisBatch><<<dim3(cdiv(a.cols, 64), cdiv(a.rows, 32), a.images), 512, 0, s>>>(
+            a.img, (int)a.pitch, a.rows, a.cols, t, hw, a.alpha, a.resp, rs, a.gx, a.gy, gs, vec_ok, img_vec_ok, b);
+    else
+        harris_image_response_kernel<R, 16, CPU, uint8_t, HarrisBatch><<<dim3(cdiv(a.cols, 64), cdiv(a.rows, 16), a.images), 256, 0, s>>>(
+            a.img, (int)a.pitch, a.rows, a.cols, t, hw, a.alpha, a.resp, rs, a.gx, a.gy, gs, vec_ok, img_vec_ok, b);
+}
+
+int harris_image_u8_launch(hipStream_t s, const HarrisU8Launch &a, int r, bool cpu) {
+    MICV_REQUIRE(r >= 1 && r <= 3 && a.images >= 1 && a.images <= 65535, "harris_image_u8_launch: window radius %d, %d images", r, a.images);
+#define MICV_HI8(RR) (cpu ? launch_harris_image_u8<RR, true> : launch_harris_image_u8<RR, false>)(s, a)
+    if (r == 1) MICV_HI8(1);
+    if (r == 2) MICV_HI8(2);
+    if (r == 3) MICV_HI8(3);
+#undef MICV_HI8
+    MICV_LAUNCH_CHECK();
+    return MICV_OK;
 }
 
 template <int R, bool CPU>
@@ -382,11 +449,11 @@ static void launch_harris_image(hipStream_t s, const float *img, int istride, in
 // One thread per pixel; only pixels with R >= threshold scan their (2d+1)^2 clamped window
 // (strictly greater than every OTHER pixel, Harris.cpp:119-135).  flag marks kept maxima for
 // the ordered compaction that follows.
-__global__ __launch_bounds__(256) void harris_nms_kernel(const float *__restrict__ resp,
-                                                          int rstride, int rows, int cols,
-                                                          double threshold, int d,
-                                                          float *__restrict__ corners, int cstride,
-                                                          unsigned long long *__restrict__ rowmask, int tiles_x) {
+__device__ __forceinline__ void harris_nms_scan_tile(const float *__restrict__ resp,
+                                                     int rstride, int rows, int cols,
+                                                     double threshold, int d,
+                                                     float *__restrict__ corners, int cstride,
+                                                     unsigned long long *__restrict__ rowmask, int tiles_x) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     const bool in = x < cols && y < rows;
@@ -414,6 +481,27 @@ __global__ __launch_bounds__(256) void harris_nms_kernel(const float *__restrict
     // a wave = 64 consecutive cells of one row: its ballot is that row segment's mask (compact.hpp)
     const unsigned long long m = __ballot(keep);
     if ((threadIdx.x & 63) == 0 && y < rows) rowmask[(size_t)y * tiles_x + blockIdx.x] = m;
+}
+
+__global__ __launch_bounds__(256) void harris_nms_kernel(const float *__restrict__ resp,
+                                                          int rstride, int rows, int cols,
+                                                          double threshold, int d,
+                                                          float *__restrict__ corners, int cstride,
+                                                          unsigned long long *__restrict__ rowmask, int tiles_x) {
+    harris_nms_scan_tile(resp, rstride, rows, cols, threshold, d, corners, cstride, rowmask, tiles_x);
+}
+
+// The image as a grid dimension (micv_harris_corners_u8_batch_dev): image blockIdx.z has its R, its sparse map and its
+// mask words at z times a distance in elements.
+struct NmsBatch {
+    size_t resp, corners, masks;
+};
+__global__ __launch_bounds__(256) void harris_nms_batch_kernel(const float *__restrict__ resp, int rstride, int rows, int cols,
+                                                                double threshold, int d, float *__restrict__ corners, int cstride,
+                                                                unsigned long long *__restrict__ rowmask, int tiles_x, NmsBatch b) {
+    const size_t z = blockIdx.z;
+    harris_nms_scan_tile(resp + z * b.resp, rstride, rows, cols, threshold, d, corners ? corners + z * b.corners : nullptr, cstride,
+                         rowmask + z * b.masks, tiles_x);
 }
 
 // LDS-tiled form for minDistance <= 16: "strictly greater than every other pixel of the clamped
@@ -453,13 +541,21 @@ __device__ __forceinline__ void nms_window4(const float (&v)[4 + 2 * D], const i
     }
 }
 
-template <int DT>
+// (With one more argument, an NmsBatch, the image is blockIdx.z: micv_harris_corners_u8_batch_dev.)
+template <int DT, typename... BATCH>
 __global__ __launch_bounds__(256) void harris_nms_tiled_kernel(const float *__restrict__ resp,
                                                                 int rstride, int rows, int cols,
                                                                 double threshold, int d_rt,
                                                                 float *__restrict__ corners,
                                                                 int cstride,
-                                                                unsigned long long *__restrict__ rowmask, int tiles_x) {
+                                                                unsigned long long *__restrict__ rowmask, int tiles_x, BATCH... batch) {
+    if constexpr (sizeof...(BATCH) > 0) {
+        const NmsBatch b = (batch, ...);
+        const size_t z = blockIdx.z;
+        resp += z * b.resp;
+        if (corners) corners += z * b.corners;
+        rowmask += z * b.masks;
+    }
     constexpr int TW = 64, TH = DT > 0 ? 32 : 16, DMAX = DT > 0 ? DT : 16;  // taller tiles re-fetch less halo
     const int d = DT > 0 ? DT : d_rt;
     __shared__ float T[(TH + 2 * DMAX) * (TW + 2 * DMAX + 1)];
@@ -625,12 +721,7 @@ __global__ void sift_keypoints_kernel(const float *__restrict__ gx, const float 
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int y = locs[2 * i], x = locs[2 * i + 1];
-    const float PI = 3.1415921636f;  // sic, Descriptors.cpp:5
-    const float a = atan2f(gy[(size_t)y * gstride + x], gx[(size_t)y * gstride + x]) * 180.f / PI;
-    kp[4 * i] = (float)x;  // cv::KeyPoint(x = corner.second, y = corner.first, size, angle), :45
-    kp[4 * i + 1] = (float)y;
-    kp[4 * i + 2] = size;
-    kp[4 * i + 3] = a;
+    sift_keypoint_store(gx[(size_t)y * gstride + x], gy[(size_t)y * gstride + x], y, x, size, kp + 4 * i);
 }
 
 }  // namespace micv
@@ -698,12 +789,70 @@ static size_t harris_refine_scratch_bytes(int rows, int cols) {
     return Carver::need(nseg, 8) + Carver::need(n, 1) + compact_scratch_bytes(n);
 }
 
+// The ordered list of one image from its mask words (rows x cdiv(cols, 64), as the NMS kernels leave them): the chained
+// scan of compact.hpp, or the three launches on flag bytes.  `scratch`: rows * cols bytes + compact_scratch_bytes(rows * cols).
+int harris_list_run(micv_ctx *ctx, hipStream_t s, const unsigned long long *rowmask, int rows, int cols, int32_t *locs_yx, int64_t cap,
+                    int64_t *count, void *scratch) {
+    const int64_t n = (int64_t)rows * cols;
+    const int tiles_x = cdiv(cols, 64);
+    const int64_t nseg = (int64_t)rows * tiles_x;
+    Carver c(scratch);
+    const int nchunks = compact_masks_chunks(nseg);
+    unsigned long long *status = nullptr;
+    unsigned *counters = nullptr;
+    if (ctx->opt[MICV_OPT_COMPACT_3PASS] <= 0 && ctx->compact_state(s, nchunks, &status, &counters) == MICV_OK) {
+        launch_compact_masks(s, rowmask, MaskYxEmit{locs_yx, tiles_x}, nseg, status, counters, cap, count);
+        MICV_LAUNCH_CHECK();
+        return MICV_OK;
+    }
+    // no state slot for this stream (or MICV_OPT_COMPACT_3PASS = 1): flag bytes and the count / scan / emit launches
+    uint8_t *flag = c.take<uint8_t>(n);
+    masks_to_flags_kernel<<<dim3(tiles_x, cdiv(rows, 4)), 256, 0, s>>>(rowmask, rows, cols, tiles_x, flag);
+    MICV_LAUNCH_CHECK();
+    // (y, x) written directly, Harris.cu:314-318 (Conv1Dto2D)
+    return ordered_compact3(s, FlagPred{flag}, YxEmit{locs_yx, cols}, n, cap, count, c.base + c.off);
+}
+size_t harris_list_scratch_bytes(int rows, int cols) {
+    const int64_t n = (int64_t)rows * cols;
+    return Carver::need(n, 1) + compact_scratch_bytes(n);
+}
+
+// The NMS launch of micv_harris_corners_u8_batch_dev: the kernels of harris_refine_run below, image = blockIdx.z.
+int harris_nms_batch_launch(micv_ctx *ctx, hipStream_t s, const float *resp, size_t resp_dist, int rows, int cols, size_t rstride,
+                            double threshold, int min_distance, float *corners, size_t corners_dist, size_t cstride,
+                            unsigned long long *rowmask, size_t mask_words, int images) {
+    MICV_REQUIRE(images >= 1 && images <= 65535 && resp_dist % 4 == 0 && corners_dist % 4 == 0, "harris_nms_batch_launch: %d images", images);
+    const int tiles_x = cdiv(cols, 64);
+    const NmsBatch b{resp_dist / 4, corners_dist / 4, mask_words};
+    if (min_distance <= 16 && !ctx->opt[MICV_OPT_NMS_SCAN]) {
+#define MICV_NMS(DT)                                                                                                 \
+    harris_nms_tiled_kernel<DT, NmsBatch><<<dim3(tiles_x, cdiv(rows, (DT) > 0 ? 32 : 16), images), 256, 0, s>>>(       \
+        resp, (int)(rstride / 4), rows, cols, threshold, min_distance, corners, (int)(cstride / 4), rowmask, tiles_x, b)
+        switch (min_distance) {
+            case 1: MICV_NMS(1); break;
+            case 2: MICV_NMS(2); break;
+            case 3: MICV_NMS(3); break;
+            case 4: MICV_NMS(4); break;
+            case 5: MICV_NMS(5); break;
+            case 6: MICV_NMS(6); break;
+            case 7: MICV_NMS(7); break;
+            case 8: MICV_NMS(8); break;
+            default: MICV_NMS(0); break;
+        }
+#undef MICV_NMS
+    } else
+        harris_nms_batch_kernel<<<dim3(tiles_x, cdiv(rows, 4), images), 256, 0, s>>>(resp, (int)(rstride / 4), rows, cols, threshold,
+                                                                                    min_distance, corners, (int)(cstride / 4), rowmask,
+                                                                                    tiles_x, b);
+    MICV_LAUNCH_CHECK();
+    return MICV_OK;
+}
+
 // harris::refineCorners on a response already on the device; `scratch` = harris_refine_scratch_bytes() of context
 // scratch.  corners (the sparse map) may be null.
 static int harris_refine_run(micv_ctx *ctx, hipStream_t s, const float *resp, int rows, int cols, size_t rstride, double threshold,
                              int min_distance, float *corners, size_t cstride, int32_t *locs_yx, int64_t cap, int64_t *count,
                              void *scratch) {
-    const int64_t n = (int64_t)rows * cols;
     // The NMS kernels leave one 64-bit mask per (row, 64-column tile) -- a wave is exactly such a row segment, its
     // ballot the mask -- and the ordered list is a chained scan over those words (compact_masks_onepass_kernel):
     // 130 k words in 32 chunks at 4K, where the flag-byte form scanned 8.3 M bytes in three launches.
@@ -736,20 +885,7 @@ static int harris_refine_run(micv_ctx *ctx, hipStream_t s, const float *resp, in
             resp, (int)(rstride / 4), rows, cols, threshold, min_distance, corners,
             (int)(cstride / 4), rowmask, tiles_x);
     MICV_LAUNCH_CHECK();
-    const int nchunks = compact_masks_chunks(nseg);
-    unsigned long long *status = nullptr;
-    unsigned *counters = nullptr;
-    if (ctx->opt[MICV_OPT_COMPACT_3PASS] <= 0 && ctx->compact_state(s, nchunks, &status, &counters) == MICV_OK) {
-        launch_compact_masks(s, rowmask, MaskYxEmit{locs_yx, tiles_x}, nseg, status, counters, cap, count);
-        MICV_LAUNCH_CHECK();
-        return MICV_OK;
-    }
-    // no state slot for this stream (or MICV_OPT_COMPACT_3PASS = 1): flag bytes and the count / scan / emit launches
-    uint8_t *flag = c.take<uint8_t>(n);
-    masks_to_flags_kernel<<<dim3(tiles_x, cdiv(rows, 4)), 256, 0, s>>>(rowmask, rows, cols, tiles_x, flag);
-    MICV_LAUNCH_CHECK();
-    // (y, x) written directly, Harris.cu:314-318 (Conv1Dto2D)
-    return ordered_compact3(s, FlagPred{flag}, YxEmit{locs_yx, cols}, n, cap, count, c.base + c.off);
+    return harris_list_run(ctx, s, rowmask, rows, cols, locs_yx, cap, count, c.base + c.off);
 }
 }  // namespace micv
 

@@ -53,4 +53,41 @@ int canny_from_u8(micv_ctx *ctx, hipStream_t s, const uint8_t *cin, size_t cstri
 // hough.hip: maxDist of Hough.cu:258-259
 size_t hough_diag(int rows, int cols);
 
+// harris.hip, for the byte entries of harris_u8.hip.  The fused image -> R launch on `images` byte images of one size
+// (image i at img + i * img_dist, pitch in bytes; R, and the gradient planes when gx is not null, at i * resp_dist /
+// i * grad_dist bytes); tall: 64x32 tiles instead of 64x16.
+struct HarrisU8Launch {
+    const uint8_t *img;
+    size_t img_dist, pitch;
+    int rows, cols, images;
+    Taps g;
+    float alpha;
+    float *resp;
+    size_t resp_dist, rstride;
+    float *gx, *gy;
+    size_t grad_dist, gstride;
+    bool tall;
+};
+int harris_image_u8_launch(hipStream_t s, const HarrisU8Launch &a, int r, bool cpu);
+// Threshold + NMS of `images` responses in one launch: sparse maps (optional) and rows * cdiv(cols, 64) mask words per
+// image, image i's at rowmask + i * mask_words.  Distances in bytes.
+int harris_nms_batch_launch(micv_ctx *ctx, hipStream_t s, const float *resp, size_t resp_dist, int rows, int cols, size_t rstride,
+                            double threshold, int min_distance, float *corners, size_t corners_dist, size_t cstride,
+                            unsigned long long *rowmask, size_t mask_words, int images);
+// One image's ordered list from its mask words, as micv_harris_refine_dev makes it; scratch: harris_list_scratch_bytes().
+int harris_list_run(micv_ctx *ctx, hipStream_t s, const unsigned long long *rowmask, int rows, int cols, int32_t *locs_yx, int64_t cap,
+                    int64_t *count, void *scratch);
+size_t harris_list_scratch_bytes(int rows, int cols);
+
+// sift::getKeypoints' row for corner (y, x) with gradient (gxv, gyv) there: cv::KeyPoint(x = corner.second,
+// y = corner.first, size, angle), Descriptors.cpp:33-45.
+__device__ __forceinline__ void sift_keypoint_store(float gxv, float gyv, int y, int x, float size, float *__restrict__ kp) {
+    const float PI = 3.1415921636f;  // sic, Descriptors.cpp:5
+    const float a = atan2f(gyv, gxv) * 180.f / PI;
+    kp[0] = (float)x;
+    kp[1] = (float)y;
+    kp[2] = size;
+    kp[3] = a;
+}
+
 }  // namespace micv

@@ -144,6 +144,112 @@ def cornersFromImage(img, sobelSize=3, windowSize=5, gaussianSigma=1.5, harrisSc
     return out
 
 
+def _pitch8(a):
+    """Row pitch in bytes of the last two dimensions of a uint8 array / tensor."""
+    if a.shape[-2] == 1:
+        return a.shape[-1]
+    return a.stride(-2) if B.is_dev(a) else a.strides[-2]
+
+
+def cornersFromImage8(img, sobelSize=3, windowSize=5, gaussianSigma=1.5, harrisScore=0.04, threshold=5e8, minDistance=5,
+                      capacity=None, ctx=None, cpu_arithmetic=False, want_gradients=True, want_response=False,
+                      want_corners=False, lazy=False, keypointSize=None):
+    """cornersFromImage on the 8-bit image itself (no convertTo(CV_32F)): a uint8 numpy array takes the `_host` entry, a
+    uint8 torch device tensor of any row stride the `_dev` one (micv_harris_corners_u8_*).  The same dict, with the bytes
+    cornersFromImage gives on the image converted to float32; keypointSize adds "keypoints" ([n, 4] float32: x, y, size,
+    angle_deg), the rows of getKeypoints at "locs" -- with or without the gradient planes."""
+    B.check2d(img, np.uint8, name="img")
+    rows, cols = img.shape
+    cap = int(capacity) if capacity is not None else rows * cols
+    c = _ctx_for(img, ctx)
+    flags = HARRIS_CPU if cpu_arithmetic else 0
+    gx = B.empty_like_shape(img, (rows, cols)) if want_gradients else None
+    gy = B.empty_like_shape(img, (rows, cols)) if want_gradients else None
+    resp = B.empty_like_shape(img, (rows, cols)) if want_response else None
+    corners = B.empty_like_shape(img, (rows, cols)) if want_corners else None
+    kp = B.empty_like_shape(img, (cap, 4)) if keypointSize is not None else None
+    rb = cols * 4
+
+    def p(a):
+        return B.ptr(a) if a is not None else None
+
+    args = (c.handle, B.ptr(img), rows, cols, _pitch8(img), int(sobelSize), int(windowSize), float(gaussianSigma), float(harrisScore),
+            flags, float(threshold), int(minDistance), p(gx), p(gy), rb, p(resp), rb, p(corners), rb)
+    ksize = float(keypointSize) if keypointSize is not None else 0.0
+    out = {}
+    if B.is_dev(img):
+        import torch
+        locs = torch.empty((cap, 2), dtype=torch.int32, device=img.device)
+        cnt = torch.zeros((1,), dtype=torch.int64, device=img.device) if lazy else B.pinned_count(img)
+        check(lib.micv_harris_corners_u8_dev(*args, locs.data_ptr(), cap, cnt.data_ptr(), ksize, p(kp), B.stream_of(img)))
+        if lazy:
+            out["locs"], out["count"] = locs, cnt
+        else:
+            n = min(B.read_count(cnt, img), cap)
+            out["locs"] = locs[:n]
+            kp = kp[:n] if kp is not None else None
+    else:
+        locs = np.empty((cap, 2), np.int32)
+        cnt = i64(0)
+        check(lib.micv_harris_corners_u8_host(*args, locs.ctypes.data, cap, C.byref(cnt), ksize, p(kp)))
+        n = min(cnt.value, cap)
+        out["locs"] = locs[:n]
+        kp = kp[:n] if kp is not None else None
+    if want_gradients:
+        out["gx"], out["gy"] = gx, gy
+    if want_response:
+        out["response"] = resp
+    if want_corners:
+        out["corners"] = corners
+    if kp is not None:
+        out["keypoints"] = kp
+    return out
+
+
+def cornersFromImage8Batch(imgs, sobelSize=3, windowSize=5, gaussianSigma=1.5, harrisScore=0.04, threshold=5e8, minDistance=5,
+                           capacity=None, ctx=None, cpu_arithmetic=False, want_gradients=True, want_response=False,
+                           want_corners=False, keypointSize=None):
+    """cornersFromImage8 on a [batch, rows, cols] uint8 device tensor of any batch and row stride, the image as a grid
+    dimension of every launch (micv_harris_corners_u8_batch_dev).  Always lazy: "locs" is [batch, capacity, 2], "count"
+    [batch] int64 on the device, "keypoints" [batch, capacity, 4], planes [batch, rows, cols]; element i holds the bytes
+    of cornersFromImage8(imgs[i], ...).  capacity defaults to rows * cols."""
+    if not B.is_dev(imgs) or not imgs.is_cuda or imgs.dim() != 3 or imgs.dtype != B.torch.uint8 or imgs.stride(2) != 1:
+        raise ValueError("imgs: need a [batch, rows, cols] uint8 device tensor with unit column stride")
+    if imgs.shape[0] < 1:
+        raise ValueError("imgs: the batch is empty")
+    import torch
+    batch, rows, cols = imgs.shape
+    cap = int(capacity) if capacity is not None else rows * cols
+    c = _ctx_for(imgs, ctx)
+    flags = HARRIS_CPU if cpu_arithmetic else 0
+
+    def plane(want):
+        return torch.empty((batch, rows, cols), dtype=torch.float32, device=imgs.device) if want else None
+
+    def p(a):
+        return a.data_ptr() if a is not None else None
+    gx, gy, resp, corners = plane(want_gradients), plane(want_gradients), plane(want_response), plane(want_corners)
+    locs = torch.empty((batch, cap, 2), dtype=torch.int32, device=imgs.device)
+    cnt = torch.zeros((batch,), dtype=torch.int64, device=imgs.device)
+    kp = torch.empty((batch, cap, 4), dtype=torch.float32, device=imgs.device) if keypointSize is not None else None
+    rb, pb = cols * 4, rows * cols * 4
+    check(lib.micv_harris_corners_u8_batch_dev(
+        c.handle, imgs.data_ptr(), imgs.stride(0) if batch > 1 else 0, batch, rows, cols, _pitch8(imgs), int(sobelSize), int(windowSize),
+        float(gaussianSigma), float(harrisScore), flags, float(threshold), int(minDistance), p(gx), p(gy), pb, rb, p(resp), pb, rb,
+        p(corners), pb, rb, locs.data_ptr(), cap, cnt.data_ptr(), float(keypointSize) if keypointSize is not None else 0.0, p(kp),
+        B.stream_of(imgs)))
+    out = {"locs": locs, "count": cnt}
+    if want_gradients:
+        out["gx"], out["gy"] = gx, gy
+    if want_response:
+        out["response"] = resp
+    if want_corners:
+        out["corners"] = corners
+    if kp is not None:
+        out["keypoints"] = kp
+    return out
+
+
 # The reference's two namespaces, for code that spells them out.
 class cpu:  # noqa: N801
     getCornerResponse = staticmethod(getCornerResponse)

@@ -344,6 +344,30 @@ inline void harrisHelperDevice(FeaturesContainer &conf) {
     micv_viz::imwrite(conf.outPrefix + conf.cornersImgPath, dots);
 }
 
+// The computing part of harrisHelper on the 8-bit picture itself: gradientX, gradientY, cornerResponse, corners and
+// cornerLocs from conf.input (CV_8UC1; an ROI with a foreign step is fine) with ONE micv_harris_corners_u8_host call --
+// 1 B per pixel goes up, and there is no convertTo(CV_32F).  Same container contents as harrisHelper's three calls.
+inline void harrisCorners8(FeaturesContainer &conf) {
+    const Mat &input = conf.input;
+    if (input.type() != micv::CV_8UC1) throw std::invalid_argument("harrisCorners8: CV_8UC1 expected");
+    const int rows = input.rows, cols = input.cols;
+    const size_t n = (size_t)rows * cols;
+    Mat gx(rows, cols, micv_shim::F32), gy(rows, cols, micv_shim::F32), resp(rows, cols, micv_shim::F32), corners(rows, cols, micv_shim::F32);
+    std::vector<int32_t> locs(2 * n);
+    int64_t count = 0;
+    micv_shim::check(micv_harris_corners_u8_host(micv_shim::context(), input.ptr<uint8_t>(), rows, cols, input.step, conf.config.sobel_kernel_size,
+                                                 (int)conf.config.window_size, conf.config.gaussian_sigma, conf.config.alpha,
+                                                 conf.useGpu ? 0 : MICV_HARRIS_CPU, conf.config.response_threshold, conf.config.min_distance,
+                                                 gx.ptr<float>(), gy.ptr<float>(), gx.step, resp.ptr<float>(), resp.step, corners.ptr<float>(),
+                                                 corners.step, locs.data(), (int64_t)n, &count, 0.f, nullptr));
+    conf.gradientX = gx;
+    conf.gradientY = gy;
+    conf.cornerResponse = resp;
+    conf.corners = corners;
+    conf.cornerLocs.clear();
+    for (int64_t i = 0; i < count; i++) conf.cornerLocs.emplace_back(locs[2 * i], locs[2 * i + 1]);
+}
+
 // siftHelper's computing steps (Solution.cpp:141-144, :166-186), shared by the two forms below
 inline void siftCompute(FeaturesContainer &img1, FeaturesContainer &img2) {
     constexpr size_t SIFT_WINDOW_SIZE = 10;
