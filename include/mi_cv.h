@@ -233,7 +233,7 @@ int micv_lk_schedule_host(int rows, int cols, int batch, int win, int max_chain,
  * row-sharded execution (a rank owns a band of rows of every level and exchanges only coarse-flow
  * halo rows with its neighbours; introtocomputervision_amd/shard.py).  prev/next are the level's
  * images (rows x cols); flow_u/flow_v the coarser level's flow (flow_rows x flow_cols, dense pitch)
- * or NULL at the coarsest level.  Output rows outside the band may or may not be written. */
+ * or NULL at the coarsest level.  Output rows outside the band are not written. */
 int micv_lk_level_dev(micv_ctx *ctx, const float *prev, const float *next, int rows, int cols,
                       size_t stride, int win, const float *flow_u, const float *flow_v,
                       int flow_rows, int flow_cols, int row_begin, int row_end, float *u, float *v,

@@ -1292,13 +1292,17 @@ int micv_lk_level_batch_dev(micv_ctx *ctx, const float *prev, const float *next,
         }
         return launch_lk_level_fused(s, a);
     }
-    // generic kernels compute the whole level, pair by pair; rows outside the band are simply not needed
+    // generic kernels compute the whole level, pair by pair; with a band the flow goes to scratch and only the band's rows
+    // are copied out (a caller's rows outside the band are not touched, as in the fused path)
+    const bool whole = row_begin == 0 && row_end == rows;
     void *scratch;
-    MICV_TRY(ctx->reserve(Carver::need(n, 4) * 4 + Carver::need(lk_generic_scratch(rows, cols), 4), &scratch));
+    MICV_TRY(ctx->reserve(Carver::need(n, 4) * (whole ? 4 : 6) + Carver::need(lk_generic_scratch(rows, cols), 4), &scratch));
     Carver carve(scratch);
     float *bu = carve.take<float>(n), *bv = carve.take<float>(n);
     float *warped = carve.take<float>(n), *tmp = carve.take<float>(n);
     float *gen = carve.take<float>(lk_generic_scratch(rows, cols));
+    float *fu = whole ? nullptr : carve.take<float>(n), *fv = whole ? nullptr : carve.take<float>(n);
+    const size_t row_bytes = (size_t)cols * 4, band_off = (size_t)row_begin * (ostride / 4);
     for (int b = 0; b < batch; b++) {
         const float *pb = prev + b * pe, *nb = next + b * pe;
         const float *fub = flow_u ? flow_u + b * fpe : nullptr, *fvb = flow_v ? flow_v + b * fpe : nullptr;
@@ -1312,8 +1316,17 @@ int micv_lk_level_batch_dev(micv_ctx *ctx, const float *prev, const float *next,
             MICV_TRY(launch_flow_expand_resize(s, fub, fvb, flow_rows, flow_cols, 0, bu, bv, rows, cols, 0, 1));
         }
         MICV_TRY(launch_warp(s, nb, (int)(stride / 4), bu, bv, cols, rows, cols, warped, cols));
-        MICV_TRY(lk_level_generic(s, pb, (int)(stride / 4), warped, cols, rows, cols, win, bu, bv, cols,
-                                  u + b * ope, v + b * ope, (int)(ostride / 4), gen, lk_generic_form(ctx)));
+        if (whole) {
+            MICV_TRY(lk_level_generic(s, pb, (int)(stride / 4), warped, cols, rows, cols, win, bu, bv, cols,
+                                      u + b * ope, v + b * ope, (int)(ostride / 4), gen, lk_generic_form(ctx)));
+            continue;
+        }
+        MICV_TRY(lk_level_generic(s, pb, (int)(stride / 4), warped, cols, rows, cols, win, bu, bv, cols, fu, fv, cols, gen,
+                                  lk_generic_form(ctx)));
+        MICV_HIP(hipMemcpy2DAsync(u + b * ope + band_off, ostride, fu + (size_t)row_begin * cols, row_bytes, row_bytes,
+                                  row_end - row_begin, hipMemcpyDeviceToDevice, s));
+        MICV_HIP(hipMemcpy2DAsync(v + b * ope + band_off, ostride, fv + (size_t)row_begin * cols, row_bytes, row_bytes,
+                                  row_end - row_begin, hipMemcpyDeviceToDevice, s));
     }
     return MICV_OK;
 }

@@ -27,6 +27,69 @@ def test_library_exports_every_declared_symbol():
     assert _capi.lib.micv_version().decode().startswith("micv")
 
 
+def header_prototypes():
+    """name -> (return kind, [argument kinds]) of every micv_* prototype in include/mi_cv.h."""
+    src = open(os.path.join(ROOT, "include", "mi_cv.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    src = re.sub(r"\btypedef\b[^;]*;", "", src)
+    pointer_types = {"micv_stream", "micv_kernel_log_fn"}
+    scalar = {"size_t": "u64", "uint64_t": "u64", "int64_t": "i64", "int": "i32", "int32_t": "i32", "uint32_t": "u32",
+              "unsigned": "u32", "unsigned int": "u32", "float": "f32", "double": "f64", "void": "void"}
+
+    def kind(decl, named):
+        if "*" in decl or "[" in decl:
+            return "p"
+        words = [w for w in decl.split() if w != "const"]
+        if named and len(words) > 1 and words[-1] not in scalar and words[-1] not in pointer_types:
+            words = words[:-1]  # the parameter's name
+        t = " ".join(words)
+        return "p" if t in pointer_types else scalar[t]
+
+    protos = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(micv_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        args = " ".join(args.split())
+        kinds = [] if args in ("", "void") else [kind(a.strip(), True) for a in args.split(",")]
+        assert name not in protos, f"{name} declared twice"
+        protos[name] = (kind(" ".join(ret.split()), False), kinds)
+    return protos
+
+
+def ctypes_kind(t):
+    import ctypes as C
+    if t is None:
+        return "void"
+    if issubclass(t, (C._Pointer, C._CFuncPtr)):
+        return "p"
+    code = {"P": "p", "z": "p", "f": "f32", "d": "f64"}.get(t._type_)
+    if code:
+        return code
+    assert t._type_ in "iIlLqQ", t
+    return ("u" if t._type_ in "ILQ" else "i") + str(8 * C.sizeof(t))
+
+
+def test_ctypes_signatures_match_the_header_kind_by_kind():
+    """Every prototype of include/mi_cv.h against _capi.SIGNATURES: argument count, the kind of every argument
+    (pointer / u64 / i64 / i32 / u32 / f32 / f64) and the kind of the return value.  A stride bound as 32 bits or a
+    double bound as a float would pass the export check above and corrupt a call."""
+    from introtocomputervision_amd import _capi
+    protos = header_prototypes()
+    assert sorted(protos) == header_functions(), sorted(set(header_functions()) ^ set(protos))
+    assert len(protos) >= 250
+    assert protos["micv_lk_level_batch_dev"][1][:5] == ["p", "p", "p", "i32", "u64"]
+    assert protos["micv_set_kernel_log"] == ("i32", ["p", "p"]) and protos["micv_div_round_up"] == ("u64", ["u64", "u64"])
+    assert protos["micv_ctx_destroy"][0] == "void" and protos["micv_version"] == ("p", [])
+    wrong = []
+    for name, (ret, kinds) in sorted(protos.items()):
+        res, args = _capi.SIGNATURES[name]
+        bound = (ctypes_kind(res), [ctypes_kind(a) for a in args])
+        if bound != (ret, kinds):
+            at = [i for i, (a, b) in enumerate(zip(bound[1], kinds)) if a != b]
+            wrong.append(f"{name}: header {ret}({len(kinds)} args), bound {bound[0]}({len(args)} args), arguments {at} differ: "
+                         f"{[(kinds[i], bound[1][i]) for i in at]}")
+    assert not wrong, "\n".join(wrong)
+
+
 def test_product_does_not_link_or_reference_the_oracle():
     import subprocess
     so = os.path.join(ROOT, "introtocomputervision_amd", "libmicv.so")
