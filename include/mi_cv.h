@@ -476,6 +476,49 @@ int micv_sift_descriptors_host(micv_ctx *ctx, const float *gx, const float *gy, 
                                size_t gstride, const float *kp_xysa, int64_t n, float *desc,
                                size_t dstride);
 
+/* The same descriptors from the 8-BIT image itself, the list length read on the device: what follows
+ * micv_harris_corners_u8_batch_dev, which ends with device-resident keypoints and counts and keeps no gradient plane.
+ * `img`: bytes at a pitch of `stride` bytes (>= cols).  kp_xysa: `cap` rows; count: a DEVICE word, or NULL for "all cap
+ * rows".  The list length is n = min(max(*count, 0), cap): a count word above cap means cap, a negative one 0.
+ *
+ * Contract.  Bytes: row k < n of desc is byte-identical to micv_sift_descriptors_dev on the planes of
+ * micv_sobel_dev(ksize 3, scale 1) of the image converted to f32, for every keypoint that entry accepts -- NaN or
+ * infinite coordinates, a size <= 0 or not finite, angles outside [0, 360) and keypoints outside the picture included
+ * (all-zero rows, as there).  The descriptor samples interior pixels only (0 < r < rows - 1, 0 < c < cols - 1), where a
+ * 3 x 3 Sobel of bytes is an integer of magnitude <= 1020: the same float in any evaluation order, with no border rule;
+ * the kernel recomputes it from the sample's eight neighbours.
+ * Counts: rows at and past n are not written.  Batch: element i is byte-identical to the single call on image i with
+ * list i.  kp_xysa is [batch][cap][4], count [batch] int64 (or NULL), image i at img + i * image_stride bytes (any value),
+ * its descriptor block at desc + i * dimage_stride bytes.
+ * Input reads: the image is read with byte loads only; its pointer, pitch and image stride need no alignment; nothing
+ * outside the `cols` bytes of each of its `rows` rows is read.  Output writes: desc follows the f32 entry's rules (dstride
+ * a multiple of 4, >= 512); nothing outside the 128 floats of a written row and nothing between a batch's descriptor
+ * blocks is written.
+ * Host and device state: no entry synchronises the host or reads a count there.  Device memory holds the bytes, the
+ * lists and the descriptors: no f32 image, no gradient plane, no context scratch.
+ * Refusals (MICV_EINVAL and a message, before anything is enqueued): batch < 1 or > 65535; descriptor blocks of one batch
+ * that overlap (dimage_stride not a multiple of 4 or below (cap - 1) * dstride + 512); the f32 entry's size limits (cap
+ * < 2^33, rows and cols <= 65535, dstride / 4 < 2^30).
+ *
+ * Kernel.  The descriptor body of the f32 entry on a byte source; the grid is sized from cap x batch, and a workgroup
+ * whose keypoint index is at or past its image's n leaves as a whole.  Every sample's eight neighbours are byte loads
+ * from the image (L1 / L2 hits within a window).  Copying a keypoint's window of up to 109 x 109 bytes to LDS first was
+ * measured and lost in every case (11.9 KB per keypoint cost occupancy at 2 and 1 waves per keypoint and the copy was
+ * never repaid; profiles/sift_u8/staged_experiment.jsonl), so there is no such form.
+ * Waves per keypoint: the host cannot see n, so the f32 entry's rule (4 below 1800 keypoints, 2 below 6144, else 1) is
+ * applied inside the kernel to n x batch, n the list length of the workgroup's own image.  The host launches every form a
+ * list of at most cap rows can pick (one when count is NULL, up to three otherwise, a form's grid covering the longest
+ * list that picks it) and the workgroups of the forms that do not apply leave at once.  The bytes do not depend on
+ * the number of waves. */
+int micv_sift_descriptors_u8_dev(micv_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, const float *kp_xysa, int64_t cap,
+                                 const int64_t *count, float *desc, size_t dstride, micv_stream stream);
+/* n host rows; uploads 1 B per pixel (micv_sift_descriptors_host: 8). */
+int micv_sift_descriptors_u8_host(micv_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, const float *kp_xysa, int64_t n,
+                                  float *desc, size_t dstride);
+int micv_sift_descriptors_u8_batch_dev(micv_ctx *ctx, const uint8_t *img, size_t image_stride, int batch, int rows, int cols, size_t stride,
+                                       const float *kp_xysa, int64_t cap, const int64_t *count, float *desc, size_t dimage_stride,
+                                       size_t dstride, micv_stream stream);
+
 /* ------------------------------------------------------------- ps2: stereo --------- */
 
 #define MICV_STEREO_COLS_2R     1 /* window of (2r+1) rows x 2r columns, DisparitySSD.cu:84 */
@@ -748,6 +791,15 @@ int micv_bf_knn2_dev(micv_ctx *ctx, const float *query, int nq, size_t qstride, 
                      micv_stream stream);
 int micv_bf_knn2_host(micv_ctx *ctx, const float *query, int nq, size_t qstride, const float *train,
                       int nt, size_t tstride, int dim, int32_t *idx2, float *dist2);
+/* The same match with both lengths read on the DEVICE: nq = min(max(*nq_count, 0), nq_cap), nt likewise (nq_cap,
+ * nt_cap >= 1).  Rows < nq of idx2 / dist2 hold the bytes of micv_bf_knn2_dev(nq, nt) when nt >= 2; with nt < 2 the empty
+ * places hold index -1 and distance +inf, as in the all-NaN case above.  Rows in [nq, nq_cap) hold {-1, -1} and
+ * {+inf, +inf}, so micv_bf_ratio_filter_dev over nq_cap rows never keeps them and returns the matches and the count of
+ * the sliced run.  Query rows at and past nq and train rows at and past nt are not read.  The grid, the train slices and
+ * the scratch are sized from the caps; nothing is read back. */
+int micv_bf_knn2_counted_dev(micv_ctx *ctx, const float *query, int nq_cap, size_t qstride, const int64_t *nq_count, const float *train,
+                             int nt_cap, size_t tstride, const int64_t *nt_count, int dim, int32_t *idx2, float *dist2,
+                             micv_stream stream);
 /* The ratio test of Solution.cpp:180-184: keep query q when dist0 < ratio * dist1.  matches_qt
  * [cap][2] = (queryIdx, trainIdx) in query order, distances [cap]; *count (device) = number kept.  The compare is
  * double(dist0) < ratio * double(dist1): a query with one finite distance (dist1 = +inf) is kept, one with none is not. */

@@ -145,6 +145,9 @@ SIGNATURES = {
     "micv_sift_keypoints_host": (i32, [vp, vp, vp, i32, i32, sz, vp, i64, f32, vp]),
     "micv_sift_descriptors_dev": (i32, [vp, vp, vp, i32, i32, sz, vp, i64, vp, sz, vp]),
     "micv_sift_descriptors_host": (i32, [vp, vp, vp, i32, i32, sz, vp, i64, vp, sz]),
+    "micv_sift_descriptors_u8_dev": (i32, [vp, vp, i32, i32, sz, vp, i64, vp, vp, sz, vp]),
+    "micv_sift_descriptors_u8_host": (i32, [vp, vp, i32, i32, sz, vp, i64, vp, sz]),
+    "micv_sift_descriptors_u8_batch_dev": (i32, [vp, vp, sz, i32, i32, i32, sz, vp, i64, vp, vp, sz, sz, vp]),
     # ps2
     "micv_disparity_ssd_dev": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, vp, sz, vp]),
     "micv_disparity_ssd_host": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, vp, sz]),
@@ -221,6 +224,7 @@ SIGNATURES = {
                                          C.POINTER(C.c_uint64), vp, vp, sz]),
     # ps4 matching
     "micv_bf_knn2_dev": (i32, [vp, vp, i32, sz, vp, i32, sz, i32, vp, vp, vp]),
+    "micv_bf_knn2_counted_dev": (i32, [vp, vp, i32, sz, vp, vp, i32, sz, vp, i32, vp, vp, vp]),
     "micv_bf_ratio_filter_dev": (i32, [vp, vp, vp, i32, f64, vp, vp, i64, vp, vp]),
     # ps4 RANSAC
     "micv_ransac_rng_create": (i32, [vp, i32, C.POINTER(vp)]),

@@ -53,6 +53,12 @@ int canny_from_u8(micv_ctx *ctx, hipStream_t s, const uint8_t *cin, size_t cstri
 // hough.hip: maxDist of Hough.cu:258-259
 size_t hough_diag(int rows, int cols);
 
+// sift.hip, for the byte entries of sift_u8.hip: the descriptor kernel on `batch` byte images of one size (image i at
+// img + i * img_dist, pitch in bytes), lists of cap rows ([batch][cap][4]) with device counts ([batch], or null: cap
+// rows each), descriptor blocks desc_dist bytes apart with rows dstride bytes apart.  cap >= 1; nothing is validated here.
+int sift_u8_launch(hipStream_t s, const uint8_t *img, size_t img_dist, int batch, int rows, int cols, size_t pitch, const float *kps,
+                   int64_t cap, const int64_t *count, float *desc, size_t desc_dist, size_t dstride);
+
 // harris.hip, for the byte entries of harris_u8.hip.  The fused image -> R launch on `images` byte images of one size
 // (image i at img + i * img_dist, pitch in bytes; R, and the gradient planes when gx is not null, at i * resp_dist /
 // i * grad_dist bytes); tall: 64x32 tiles instead of 64x16.

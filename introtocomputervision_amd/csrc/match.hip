@@ -40,11 +40,28 @@ typedef float mf2 __attribute__((ext_vector_type(2)));
 typedef float mf4 __attribute__((ext_vector_type(4)));
 constexpr int kQT = 64, kTT = 128, kDC = 32;
 
-__global__ __launch_bounds__(256) void bf_knn2_kernel(const float *__restrict__ query, int nq,
+// COUNTED (micv_bf_knn2_counted_dev): nq_cap / nt_cap size the grid, the slices and the partial lists; the lengths
+// themselves are device words, clamped to [0, cap].  A workgroup whose queries all lie at or past the count leaves as a whole
+// before any barrier; a slice at or past the train count runs no pass and leaves its queries' lists empty.
+__device__ __forceinline__ int bf_clamped_count(const int64_t *count, int cap) {
+    const int64_t c = *count;
+    return c < 0 ? 0 : (c < cap ? (int)c : cap);
+}
+
+template <bool COUNTED>
+__global__ __launch_bounds__(256) void bf_knn2_kernel(const float *__restrict__ query, int nq_cap,
                                                        int qstride, const float *__restrict__ train,
-                                                       int nt, int tstride, int dim, int slice_rows,
+                                                       int nt_cap, int tstride, int dim, int slice_rows,
                                                        int32_t *__restrict__ part_i,
-                                                       float *__restrict__ part_d, int vec_ok) {
+                                                       float *__restrict__ part_d, int vec_ok,
+                                                       const int64_t *__restrict__ nq_count,
+                                                       const int64_t *__restrict__ nt_count) {
+    int nq = nq_cap, nt = nt_cap;
+    if constexpr (COUNTED) {
+        nq = bf_clamped_count(nq_count, nq_cap);
+        nt = bf_clamped_count(nt_count, nt_cap);
+        if ((int)blockIdx.x * kQT >= nq) return;
+    }
     __shared__ __attribute__((aligned(16))) float Qt[kDC][kQT];
     __shared__ __attribute__((aligned(16))) float Tt[kDC][kTT];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
@@ -154,21 +171,26 @@ __global__ __launch_bounds__(256) void bf_knn2_kernel(const float *__restrict__ 
         for (int g = 0; g < 16; g++)
             for (int sidx = 0; sidx < 2; sidx++)
                 if (mi[g][tid][sidx] >= 0) m.push(md[g][tid][sidx], mi[g][tid][sidx]);
-        const size_t o = ((size_t)blockIdx.y * nq + q0 + tid) * 2;
+        const size_t o = ((size_t)blockIdx.y * nq_cap + q0 + tid) * 2;
         part_i[o] = m.i0; part_i[o + 1] = m.i1;
         part_d[o] = m.d0; part_d[o + 1] = m.d1;
     }
 }
 
 // Top-2 over the slices' partial top-2 lists (slice order = index order), then the square roots.
+// COUNTED: rows at and past the query count get {-1, -1} and {+inf, +inf} (their partial lists were never written).
+template <bool COUNTED>
 __global__ __launch_bounds__(256) void bf_merge_kernel(const int32_t *__restrict__ part_i,
                                                         const float *__restrict__ part_d, int nq,
                                                         int slices, int32_t *__restrict__ idx2,
-                                                        float *__restrict__ dist2) {
+                                                        float *__restrict__ dist2, const int64_t *__restrict__ nq_count) {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= nq) return;
     Top2 m;
     m.init();
+    if constexpr (COUNTED) {
+        if (q >= bf_clamped_count(nq_count, nq)) slices = 0;
+    }
     for (int s = 0; s < slices; s++)
         for (int k = 0; k < 2; k++) {
             const size_t o = ((size_t)s * nq + q) * 2 + k;
@@ -207,14 +229,9 @@ __global__ void bf_emit_kernel(const int32_t *__restrict__ sel, const int64_t *_
 
 using namespace micv;
 
-extern "C" {
-
-int micv_bf_knn2_dev(micv_ctx *ctx, const float *query, int nq, size_t qstride, const float *train,
-                     int nt, size_t tstride, int dim, int32_t *idx2, float *dist2,
-                     micv_stream stream) {
-    MICV_REQUIRE(ctx && query && train && idx2 && dist2, "micv_bf_knn2: null argument");
-    MICV_REQUIRE(nq > 0 && nt >= 2 && dim > 0, "micv_bf_knn2: need nq > 0, nt >= 2, dim > 0");
-    MICV_REQUIRE(stride_ok(qstride, dim, 4) && stride_ok(tstride, dim, 4), "micv_bf_knn2: bad stride");
+// Both matcher entries: nq / nt are the lengths (counts null) or the capacities the launch is sized from.
+static int bf_knn2_run(micv_ctx *ctx, const float *query, int nq, size_t qstride, const int64_t *nq_count, const float *train, int nt,
+                       size_t tstride, const int64_t *nt_count, int dim, int32_t *idx2, float *dist2, micv_stream stream) {
     MICV_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     // slices of the train set: enough workgroups for 2 - 4 per CU, whole 128-row passes per slice
@@ -234,13 +251,40 @@ int micv_bf_knn2_dev(micv_ctx *ctx, const float *query, int nq, size_t qstride, 
     float *part_d = c.take<float>((size_t)slices * nq * 2);
     const int vec_ok = ((reinterpret_cast<uintptr_t>(query) | reinterpret_cast<uintptr_t>(train) | qstride | tstride) & 15) == 0 &&
                        (dim & 3) == 0;
-    bf_knn2_kernel<<<dim3(qblocks, slices), 256, 0, s>>>(query, nq, (int)(qstride / 4), train, nt,
-                                                         (int)(tstride / 4), dim, slice_rows, part_i,
-                                                         part_d, vec_ok);
-    MICV_LAUNCH_CHECK();
-    bf_merge_kernel<<<cdiv(nq, 256), 256, 0, s>>>(part_i, part_d, nq, slices, idx2, dist2);
+    if (nq_count) {
+        bf_knn2_kernel<true><<<dim3(qblocks, slices), 256, 0, s>>>(query, nq, (int)(qstride / 4), train, nt, (int)(tstride / 4), dim,
+                                                                   slice_rows, part_i, part_d, vec_ok, nq_count, nt_count);
+        MICV_LAUNCH_CHECK();
+        bf_merge_kernel<true><<<cdiv(nq, 256), 256, 0, s>>>(part_i, part_d, nq, slices, idx2, dist2, nq_count);
+    } else {
+        bf_knn2_kernel<false><<<dim3(qblocks, slices), 256, 0, s>>>(query, nq, (int)(qstride / 4), train, nt,
+                                                                    (int)(tstride / 4), dim, slice_rows, part_i,
+                                                                    part_d, vec_ok, nullptr, nullptr);
+        MICV_LAUNCH_CHECK();
+        bf_merge_kernel<false><<<cdiv(nq, 256), 256, 0, s>>>(part_i, part_d, nq, slices, idx2, dist2, nullptr);
+    }
     MICV_LAUNCH_CHECK();
     return MICV_OK;
+}
+
+extern "C" {
+
+int micv_bf_knn2_dev(micv_ctx *ctx, const float *query, int nq, size_t qstride, const float *train,
+                     int nt, size_t tstride, int dim, int32_t *idx2, float *dist2,
+                     micv_stream stream) {
+    MICV_REQUIRE(ctx && query && train && idx2 && dist2, "micv_bf_knn2: null argument");
+    MICV_REQUIRE(nq > 0 && nt >= 2 && dim > 0, "micv_bf_knn2: need nq > 0, nt >= 2, dim > 0");
+    MICV_REQUIRE(stride_ok(qstride, dim, 4) && stride_ok(tstride, dim, 4), "micv_bf_knn2: bad stride");
+    return bf_knn2_run(ctx, query, nq, qstride, nullptr, train, nt, tstride, nullptr, dim, idx2, dist2, stream);
+}
+
+int micv_bf_knn2_counted_dev(micv_ctx *ctx, const float *query, int nq_cap, size_t qstride, const int64_t *nq_count, const float *train,
+                             int nt_cap, size_t tstride, const int64_t *nt_count, int dim, int32_t *idx2, float *dist2,
+                             micv_stream stream) {
+    MICV_REQUIRE(ctx && query && train && idx2 && dist2 && nq_count && nt_count, "micv_bf_knn2_counted: null argument");
+    MICV_REQUIRE(nq_cap > 0 && nt_cap > 0 && dim > 0, "micv_bf_knn2_counted: need nq_cap > 0, nt_cap > 0, dim > 0");
+    MICV_REQUIRE(stride_ok(qstride, dim, 4) && stride_ok(tstride, dim, 4), "micv_bf_knn2_counted: bad stride");
+    return bf_knn2_run(ctx, query, nq_cap, qstride, nq_count, train, nt_cap, tstride, nt_count, dim, idx2, dist2, stream);
 }
 
 int micv_bf_ratio_filter_dev(micv_ctx *ctx, const int32_t *idx2, const float *dist2, int nq,

@@ -19,7 +19,7 @@
 // 64-bit LDS atomics.  The 128-term norms are summed left to right by one lane (the contract).
 #include <cfloat>
 
-#include "common.hpp"
+#include "kernels.hpp"
 #include "sincos_deg.hpp"
 
 namespace micv {
@@ -131,33 +131,105 @@ __device__ __forceinline__ void keypoint_sync() {
 // workgroup), 2 in between, 4 when there are few (one keypoint per workgroup, the window's passes dealt round-robin
 // to the waves, each wave adding into its own histogram copies) -- a lone wave takes ~0.13 ms for a
 // 107x107 window, which is all the latency a small keypoint list would ever see.
+//
+// The body is one piece of code for two gradient sources.  SiftPlanes reads the two f32 planes of harris::getGradients.
+// SiftBytes recomputes the 3 x 3 Sobel pair from the bytes of the 8-bit image (micv_sift_descriptors_u8_*): only interior
+// pixels are ever sampled (sift_test), where the Sobel value is an integer of magnitude <= 1020, the float the plane
+// holds; the eight neighbours of a sample are byte loads from the image itself.  (Copying the keypoint's window to LDS
+// first was tried and lost everywhere: profiles/sift_u8/staged_experiment.jsonl.)
+constexpr int LEN = SD * SD * SN;
+struct SiftLds {
+    unsigned long long (*hist_all)[COPIES * SHIST];
+    unsigned (*scratch_all)[LEN];
+    float *bound_all;
+};
+
+struct SiftPlanes {
+    static constexpr bool kBytes = false;
+    const float *__restrict__ gx, *__restrict__ gy;
+    int gstride;
+    struct Raw { float dx, dy; };
+    // (rejected samples read element 0)
+    __device__ __forceinline__ void load(bool ok, int r, int c, Raw &v) const {
+        const size_t off = ok ? (size_t)r * gstride + c : 0;
+        v.dx = gx[off];
+        v.dy = gy[off];
+    }
+    static __device__ __forceinline__ void resolve(const Raw &v, float &dx, float &dy) { dx = v.dx; dy = v.dy; }
+};
+
+// The 3 x 3 neighbourhood of one pixel, centre left out.
+struct SiftNb { int a, b, c, d, f, g, h, i; };
+struct SiftPxGlobal {  // the image itself; pitch in bytes
+    const uint8_t *__restrict__ img;
+    size_t pitch;
+    __device__ __forceinline__ int px(int r, int c) const { return img[(size_t)r * pitch + c]; }
+    // (rejected samples read around pixel (1, 1): sweep 2 only runs when the interior is not empty)
+    __device__ __forceinline__ void nb(bool ok, int r, int c, SiftNb &v) const {
+        const uint8_t *p = img + (ok ? (size_t)r * pitch + c : pitch + 1);
+        const uint8_t *u = p - pitch, *d = p + pitch;
+        v.a = u[-1]; v.b = u[0]; v.c = u[1]; v.d = p[-1]; v.f = p[1]; v.g = d[-1]; v.h = d[0]; v.i = d[1];
+    }
+};
+struct SiftBytes {
+    static constexpr bool kBytes = true;
+    SiftPxGlobal p;
+    using Raw = SiftNb;
+    __device__ __forceinline__ void load(bool ok, int r, int c, Raw &v) const { p.nb(ok, r, c, v); }
+    // harris::getGradients' 3 x 3 Sobel (right minus left, down minus up) in integers
+    static __device__ __forceinline__ void resolve(const Raw &v, float &dx, float &dy) {
+        dx = (float)((v.c + 2 * v.f + v.i) - (v.a + 2 * v.d + v.g));
+        dy = (float)((v.g + 2 * v.h + v.i) - (v.a + 2 * v.b + v.c));
+    }
+    // max(|gx|, |gy|) over four rows from r (those up to r_hi) at column c: six rows of three bytes
+    __device__ __forceinline__ int absmax4(int r, int r_hi, int c) const {
+        int hd[6], hs[6];
+#pragma unroll
+        for (int m = 0; m < 6; m++) {
+            const int rr = r - 1 + m <= r_hi + 1 ? r - 1 + m : r_hi + 1;
+            const int a = p.px(rr, c - 1), b = p.px(rr, c), d = p.px(rr, c + 1);
+            hd[m] = d - a;
+            hs[m] = a + 2 * b + d;
+        }
+        int best = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (r + k > r_hi) continue;  // (rows past r_hi were clamped: not a neighbourhood)
+            const int vx = abs(hd[k] + 2 * hd[k + 1] + hd[k + 2]), vy = abs(hs[k + 2] - hs[k]);
+            const int m = vx > vy ? vx : vy;
+            best = m > best ? m : best;
+        }
+        return best;
+    }
+};
+
+// Sweep 1 on bytes, the walk of the f32 form: a wave takes whole rows of the square, four at a time.
 template <int WPK>
-__global__ __launch_bounds__(256) void sift_descriptor_kernel(const float *__restrict__ gx,
-                                                               const float *__restrict__ gy, int gstride,
-                                                               int rows, int cols,
-                                                               const float *__restrict__ kps, long long n,
-                                                               float *__restrict__ desc, int dstride) {
-    constexpr int G = 4 / WPK;  // keypoints per workgroup
-    constexpr int LEN = SD * SD * SN;
-    __shared__ unsigned long long hist_all[4][COPIES * SHIST];
-    // per wave: the queue of sweep 2; after it (and a keypoint_sync) the first G of these are the keypoints' float rows
-    __shared__ unsigned scratch_all[4][LEN];
-    __shared__ float bound_all[4];
+__device__ __forceinline__ float sift_bound_bytes(const SiftBytes &src, int r_lo, int r_hi, int c_lo, int c_hi, int lane, int sub) {
+    int best = 0;
+    for (int r = r_lo + 4 * sub; r <= r_hi; r += 4 * WPK)
+        for (int c = c_lo + lane; c <= c_hi; c += 64) {
+            const int m = src.absmax4(r, r_hi, c);
+            best = m > best ? m : best;
+        }
+    return (float)best;
+}
+
+template <int WPK, class Src>
+__device__ __forceinline__ void sift_sweep2(const Src &src, int rows, int cols, const SiftGeom &g, bool flat, double fx_scale, int lane,
+                                            int sub, unsigned long long *hist, unsigned *queue);
+
+// One keypoint's descriptor by the WPK waves of group `grp`: histogram, finalisation, the row `out`.
+template <int WPK, class Src>
+__device__ __forceinline__ void sift_descriptor_body(const Src &src, int rows, int cols,
+                                                     const SiftGeom &g, float *__restrict__ out, const SiftLds &L) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = wave / WPK, sub = wave - grp * WPK;
-    long long k = (long long)blockIdx.x * G + grp;
-    if constexpr (WPK == 1) {
-        if (k >= n) return;  // whole waves leave, there is no workgroup barrier below
-    } else {
-        k = k < n ? k : n - 1;  // WPK 2, odd n: the last workgroup's second pair of waves repeats the last keypoint (same bytes)
-    }
-    unsigned long long *hist = hist_all[wave];
-    float *dst = reinterpret_cast<float *>(scratch_all[grp]);
-    unsigned *queue = scratch_all[wave];
-    float *out = desc + (size_t)k * dstride;
-    const SiftGeom g = sift_geometry(kps + 4 * k, rows, cols);
+    unsigned long long *hist = L.hist_all[wave];
+    float *dst = reinterpret_cast<float *>(L.scratch_all[grp]);
+    unsigned *queue = L.scratch_all[wave];
+    float *bound_all = L.bound_all;
     for (int t = lane; t < COPIES * SHIST; t += 64) hist[t] = 0ull;
-    const int side = 2 * g.radius + 1;
 
     // sweep 1: a bound on every contribution, 2 * max(|gx|, |gy|) over the window's bounding square
     // inside the image interior (no rotation, no square root: ~8 instructions per sample)
@@ -168,7 +240,11 @@ __global__ __launch_bounds__(256) void sift_descriptor_kernel(const float *__res
         // two dependent loads per sample (3.6 k of the kernel's 30 k instructions per keypoint at size 10)
         const int c_lo = g.px - g.radius > 1 ? g.px - g.radius : 1, c_hi = g.px + g.radius < cols - 2 ? g.px + g.radius : cols - 2;
         const int r_lo = g.py - g.radius > 1 ? g.py - g.radius : 1, r_hi = g.py + g.radius < rows - 2 ? g.py + g.radius : rows - 2;
-        if (g.valid && c_lo <= c_hi) {
+        if constexpr (Src::kBytes) {
+            if (g.valid && c_lo <= c_hi) bound = sift_bound_bytes<WPK>(src, r_lo, r_hi, c_lo, c_hi, lane, sub);
+        } else if (g.valid && c_lo <= c_hi) {
+            const float *__restrict__ gx = src.gx, *__restrict__ gy = src.gy;
+            const int gstride = src.gstride;
             for (int r = r_lo + 4 * sub; r <= r_hi; r += 4 * WPK) {
                 for (int c = c_lo + lane; c <= c_hi; c += 64) {
                     float ax[4], ay[4];
@@ -212,6 +288,49 @@ __global__ __launch_bounds__(256) void sift_descriptor_kernel(const float *__res
     const int sh = 40 - e;
     const double fx_scale = ldexp(1.0, sh);
 
+    sift_sweep2<WPK>(src, rows, cols, g, flat, fx_scale, lane, sub, hist, queue);
+    keypoint_sync<WPK>();
+
+    // finalize: circular orientation axis, spatial border bins dropped, back to float
+    const unsigned long long *hist0 = L.hist_all[grp * WPK];  // the keypoint's WPK x COPIES copies are contiguous
+    for (int t = 64 * sub + lane; t < LEN; t += 64 * WPK) {
+        const int cell = t / SN, o = t - cell * SN;
+        const int ci = cell / SD, cj = cell - ci * SD;
+        const int idx = (ci * SD + cj) * (SN + 1);
+        long long h = 0;
+#pragma unroll
+        for (int cp = 0; cp < COPIES * WPK; cp++) {
+            h += (long long)hist0[cp * SHIST + idx + o];
+            if (o == 0) h += (long long)hist0[cp * SHIST + idx + SN];  // the orientation axis is circular
+        }
+        dst[t] = ldexpf((float)h, e - 40);
+    }
+    keypoint_sync<WPK>();
+    if (flat) return;  // (after the last barrier)
+    // the two 128-term norms, left to right in float (every lane computes them: uniform, no broadcast)
+    float nrm2 = 0.f;
+    for (int t = 0; t < LEN; t++) nrm2 += dst[t] * dst[t];
+    const float thr = sqrtf(nrm2) * 0.2f;  // SIFT_DESCR_MAG_THR
+    nrm2 = 0.f;
+    for (int t = 0; t < LEN; t++) {
+        const float d0 = dst[t];
+        const float val = d0 < thr ? d0 : thr;
+        nrm2 += val * val;
+    }
+    const float nrm = sqrtf(nrm2);
+    const float scale = 512.f / (nrm > FLT_EPSILON ? nrm : FLT_EPSILON);  // SIFT_INT_DESCR_FCTR
+    for (int t = 64 * sub + lane; t < LEN; t += 64 * WPK) {
+        const float d0 = dst[t];
+        const float val = d0 < thr ? d0 : thr;
+        const float v = rintf(val * scale);  // saturate_cast<uchar>
+        out[t] = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
+    }
+}
+
+template <int WPK, class Src>
+__device__ __forceinline__ void sift_sweep2(const Src &src, int rows, int cols, const SiftGeom &g, bool flat, double fx_scale, int lane,
+                                            int sub, unsigned long long *hist, unsigned *queue) {
+    const int side = 2 * g.radius + 1;
     // sweep 2: eight trilinear shares per sample, fixed-point adds into the wave's histogram
     // (the wave's zero fill of its own copies is ordered before its own atomics: same wave, in order)
     // A lone wave is bound by the latency of its gradient loads (one dependent L2 / HBM round trip per
@@ -268,7 +387,8 @@ __global__ __launch_bounds__(256) void sift_descriptor_kernel(const float *__res
             // this wave's share of the passes (four queued blocks each): every WPK-th one, U at a time
             const int npass = (count + 3) >> 2;
             for (int p0 = sub; p0 < npass; p0 += U * WPK) {
-            float rbin[U], cbin[U], dx[U], dy[U], w[U];
+            float rbin[U], cbin[U], w[U];
+            typename Src::Raw raw[U];
             bool ok[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
@@ -280,16 +400,16 @@ __global__ __launch_bounds__(256) void sift_descriptor_kernel(const float *__res
                 const int i = -g.radius + 4 * (int)(packed >> 16) + ly, j = -g.radius + 4 * (int)(packed & 0xffffu) + lx;
                 ok[u] = slot < count && i <= g.radius && j <= g.radius &&
                         sift_test(rows, cols, g, i, j, rbin[u], cbin[u], w[u]);
-                const size_t off = ok[u] ? (size_t)(g.py + i) * gstride + (g.px + j) : 0;
-                dx[u] = gx[off];
-                dy[u] = gy[off];  // (negated below: a negation here would wait for the load inside the batch)
+                src.load(ok[u], g.py + i, g.px + j, raw[u]);  // (resolved below: arithmetic here would wait for the load inside the batch)
             }
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 if (!ok[u]) continue;
-                const float dyu = -dy[u];  // SIFT's dy is "up minus down"
-                const float mag = sqrtf(dx[u] * dx[u] + dyu * dyu) * exp_neg(w[u]);
-                float obin = (fast_atan2_deg(dyu, dx[u]) - g.ori) * ((float)SN / 360.f);
+                float dxu, dyr;
+                Src::resolve(raw[u], dxu, dyr);
+                const float dyu = -dyr;  // SIFT's dy is "up minus down"
+                const float mag = sqrtf(dxu * dxu + dyu * dyu) * exp_neg(w[u]);
+                float obin = (fast_atan2_deg(dyu, dxu) - g.ori) * ((float)SN / 360.f);
                 float rb = rbin[u], cb = cbin[u];
                 const float r0f = floorf(rb), c0f = floorf(cb), o0f = floorf(obin);
                 rb -= r0f;
@@ -315,6 +435,7 @@ __global__ __launch_bounds__(256) void sift_descriptor_kernel(const float *__res
                 const bool r_lo = r0 >= 0, r_hi = r0 < SD - 1, c_lo = c0 >= 0, c_hi = c0 < SD - 1;
                 const int idx = (r0 * SD + c0) * (SN + 1) + o0 + (lane & (COPIES - 1)) * SHIST;
                 constexpr int DC = SN + 1, DR = SD * (SN + 1);
+                if constexpr (!Src::kBytes) {  // (a Sobel value of bytes is a finite integer)
                 if (mag != mag) {
                     const unsigned long long ind = 0x8000000000000000ull;
                     if (r_lo && c_lo) { atomicAdd(&hist[idx], ind); atomicAdd(&hist[idx + 1], ind); }
@@ -322,6 +443,7 @@ __global__ __launch_bounds__(256) void sift_descriptor_kernel(const float *__res
                     if (r_hi && c_lo) { atomicAdd(&hist[idx + DR], ind); atomicAdd(&hist[idx + DR + 1], ind); }
                     if (r_hi && c_hi) { atomicAdd(&hist[idx + DR + DC], ind); atomicAdd(&hist[idx + DR + DC + 1], ind); }
                     continue;
+                }
                 }
                 // llrintf(ldexpf(v, sh)) for 0 <= v * 2^sh < 2^41: one double fma onto 2^52 rounds to the
                 // nearest-even integer and leaves it in the low mantissa bits
@@ -337,42 +459,103 @@ __global__ __launch_bounds__(256) void sift_descriptor_kernel(const float *__res
             __builtin_amdgcn_wave_barrier();
         }
     }
-    keypoint_sync<WPK>();
+}
 
-    // finalize: circular orientation axis, spatial border bins dropped, back to float
-    const unsigned long long *hist0 = hist_all[grp * WPK];  // the keypoint's WPK x COPIES copies are contiguous
-    for (int t = 64 * sub + lane; t < LEN; t += 64 * WPK) {
-        const int cell = t / SN, o = t - cell * SN;
-        const int ci = cell / SD, cj = cell - ci * SD;
-        const int idx = (ci * SD + cj) * (SN + 1);
-        long long h = 0;
-#pragma unroll
-        for (int cp = 0; cp < COPIES * WPK; cp++) {
-            h += (long long)hist0[cp * SHIST + idx + o];
-            if (o == 0) h += (long long)hist0[cp * SHIST + idx + SN];  // the orientation axis is circular
-        }
-        dst[t] = ldexpf((float)h, e - 40);
+template <int WPK>
+__global__ __launch_bounds__(256) void sift_descriptor_kernel(const float *__restrict__ gx,
+                                                               const float *__restrict__ gy, int gstride,
+                                                               int rows, int cols,
+                                                               const float *__restrict__ kps, long long n,
+                                                               float *__restrict__ desc, int dstride) {
+    constexpr int G = 4 / WPK;  // keypoints per workgroup
+    __shared__ unsigned long long hist_all[4][COPIES * SHIST];
+    // per wave: the queue of sweep 2; after it (and a keypoint_sync) the first G of these are the keypoints' float rows
+    __shared__ unsigned scratch_all[4][LEN];
+    __shared__ float bound_all[4];
+    const int wave = threadIdx.x >> 6;
+    const int grp = wave / WPK;
+    long long k = (long long)blockIdx.x * G + grp;
+    if constexpr (WPK == 1) {
+        if (k >= n) return;  // whole waves leave, there is no workgroup barrier below
+    } else {
+        k = k < n ? k : n - 1;  // WPK 2, odd n: the last workgroup's second pair of waves repeats the last keypoint (same bytes)
     }
-    keypoint_sync<WPK>();
-    if (flat) return;  // (after the last barrier)
-    // the two 128-term norms, left to right in float (every lane computes them: uniform, no broadcast)
-    float nrm2 = 0.f;
-    for (int t = 0; t < LEN; t++) nrm2 += dst[t] * dst[t];
-    const float thr = sqrtf(nrm2) * 0.2f;  // SIFT_DESCR_MAG_THR
-    nrm2 = 0.f;
-    for (int t = 0; t < LEN; t++) {
-        const float d0 = dst[t];
-        const float val = d0 < thr ? d0 : thr;
-        nrm2 += val * val;
+    const SiftGeom g = sift_geometry(kps + 4 * k, rows, cols);
+    const SiftPlanes src{gx, gy, gstride};
+    sift_descriptor_body<WPK>(src, rows, cols, g, desc + (size_t)k * dstride, SiftLds{hist_all, scratch_all, bound_all});
+}
+
+// The byte form.  Grid: x = workgroups of G keypoints, y = image.  n, this image's list length, is read here, and so is
+// the number of waves per keypoint (sift_u8_wpk): the host launches every form the caps admit and the workgroups of
+// the forms that do not apply leave at once, as do those at and past n -- whole workgroups, before any barrier.
+struct SiftU8Args {
+    const uint8_t *img;
+    size_t img_dist, pitch;  // bytes
+    int rows, cols, batch;
+    const float *kps;      // [batch][cap][4]
+    long long cap;
+    const int64_t *count;  // [batch], or null: cap
+    float *desc;
+    size_t desc_dist;  // floats
+    int dstride;       // floats
+};
+
+// Waves per keypoint of the byte entries: the f32 entry's rule (micv_sift_descriptors_dev) on n * batch, n the list
+// length of the workgroup's own image -- what the launch holds if every image has as many.
+__host__ __device__ inline int sift_u8_wpk(long long n, int batch) {
+    const long long total = n * batch;
+    return total < 1800 ? 4 : (total < 6144 ? 2 : 1);
+}
+
+template <int WPK>
+__global__ __launch_bounds__(256) void sift_descriptor_u8_kernel(const SiftU8Args a) {
+    constexpr int G = 4 / WPK;
+    __shared__ unsigned long long hist_all[4][COPIES * SHIST];
+    __shared__ unsigned scratch_all[4][LEN];
+    __shared__ float bound_all[4];
+    const size_t z = blockIdx.y;
+    long long n = a.cap;
+    if (a.count) {
+        const long long c = a.count[z];
+        n = c < 0 ? 0 : (c < a.cap ? c : a.cap);
     }
-    const float nrm = sqrtf(nrm2);
-    const float scale = 512.f / (nrm > FLT_EPSILON ? nrm : FLT_EPSILON);  // SIFT_INT_DESCR_FCTR
-    for (int t = 64 * sub + lane; t < LEN; t += 64 * WPK) {
-        const float d0 = dst[t];
-        const float val = d0 < thr ? d0 : thr;
-        const float v = rintf(val * scale);  // saturate_cast<uchar>
-        out[t] = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
+    if (sift_u8_wpk(n, a.batch) != WPK) return;
+    if ((long long)blockIdx.x * G >= n) return;  // (n == 0 included: no row is read)
+    const int grp = (int)(threadIdx.x >> 6) / WPK;
+    long long k = (long long)blockIdx.x * G + grp;
+    if constexpr (WPK == 1) {
+        if (k >= n) return;  // whole waves leave, there is no workgroup barrier below
+    } else {
+        k = k < n ? k : n - 1;  // WPK 2, odd n: the second pair of waves repeats the last keypoint (same bytes; n >= 1 here)
     }
+    const uint8_t *img = a.img + z * a.img_dist;
+    const SiftGeom g = sift_geometry(a.kps + (z * (size_t)a.cap + k) * 4, a.rows, a.cols);
+    const SiftBytes src{{img, a.pitch}};
+    sift_descriptor_body<WPK>(src, a.rows, a.cols, g, a.desc + z * a.desc_dist + (size_t)k * a.dstride,
+                              SiftLds{hist_all, scratch_all, bound_all});
+}
+
+int sift_u8_launch(hipStream_t s, const uint8_t *img, size_t img_dist, int batch, int rows, int cols, size_t pitch, const float *kps,
+                   int64_t cap, const int64_t *count, float *desc, size_t desc_dist, size_t dstride) {
+    const SiftU8Args a{img, img_dist, pitch, rows, cols, batch, kps, (long long)cap, count, desc, desc_dist / 4, (int)(dstride / 4)};
+    // The forms a list of at most cap rows can pick; without counts the list IS cap rows and one form is launched.  A
+    // form's grid covers the longest list that picks it.
+    const int lo = sift_u8_wpk(cap, batch), hi = count ? 4 : lo;
+    if (hi >= 4 && lo <= 4) {
+        const int64_t most = count ? (cap < 1799 ? cap : 1799) : cap;
+        sift_descriptor_u8_kernel<4><<<dim3((unsigned)most, batch), 256, 0, s>>>(a);
+        MICV_LAUNCH_CHECK();
+    }
+    if (hi >= 2 && lo <= 2) {
+        const int64_t most = count ? (cap < 6143 ? cap : 6143) : cap;
+        sift_descriptor_u8_kernel<2><<<dim3((unsigned)((most + 1) / 2), batch), 256, 0, s>>>(a);
+        MICV_LAUNCH_CHECK();
+    }
+    if (lo == 1) {
+        sift_descriptor_u8_kernel<1><<<dim3((unsigned)((cap + 3) / 4), batch), 256, 0, s>>>(a);
+        MICV_LAUNCH_CHECK();
+    }
+    return MICV_OK;
 }
 
 }  // namespace micv

@@ -337,3 +337,59 @@ def computeDescriptors(gradX, gradY, keypoints, ctx=None):
     check(lib.micv_sift_descriptors_host(c.handle, B.ptr(gradX), B.ptr(gradY), rows, cols,
                                          B.stride_bytes(gradX), kp.ctypes.data, n, desc.ctypes.data, 512))
     return desc
+
+
+def computeDescriptors8(img, keypoints, count=None, ctx=None):
+    """computeDescriptors on the 8-bit image itself (micv_sift_descriptors_u8_*): no float image and no gradient planes,
+    the 3x3 Sobel pair of every sample is recomputed from the bytes.  A uint8 numpy array with [n, 4] keypoints takes the
+    `_host` entry (count: an int or None); a uint8 CUDA tensor of any row stride with [cap, 4] CUDA keypoints the `_dev`
+    one, count a 1-element int64 CUDA word (None: every row) that is read on the device.  -> [cap, 128] float32 with the
+    bytes of computeDescriptors(*getGradients(img as float32, 3, 1.0), keypoints) in rows below min(count, cap); device rows
+    past the count are not written (the tensor is zero-filled first)."""
+    B.check2d(img, np.uint8, name="img")
+    rows, cols = img.shape
+    c = _ctx_for(img, ctx)
+    if B.is_dev(img):
+        import torch
+        if not (B.is_dev(keypoints) and keypoints.is_cuda and keypoints.device == img.device):
+            raise ValueError("keypoints: must be a CUDA tensor on img's device (numpy inputs take the host path)")
+        kp = keypoints.to(torch.float32).contiguous().reshape(-1, 4)
+        cap = int(kp.shape[0])
+        if count is not None and not (B.is_dev(count) and count.is_cuda and count.device == img.device and count.dtype == torch.int64
+                                      and count.numel() == 1):
+            raise ValueError("count: a 1-element int64 CUDA tensor on img's device expected")
+        desc = torch.zeros((cap, 128), dtype=torch.float32, device=img.device)
+        check(lib.micv_sift_descriptors_u8_dev(c.handle, B.ptr(img), rows, cols, _pitch8(img), kp.data_ptr(), cap,
+                                               count.data_ptr() if count is not None else None, desc.data_ptr(), 512, B.stream_of(img)))
+        return desc
+    kp = np.ascontiguousarray(keypoints, dtype=np.float32).reshape(-1, 4)
+    n = kp.shape[0] if count is None else max(0, min(int(count), kp.shape[0]))
+    desc = np.zeros((kp.shape[0], 128), np.float32)
+    check(lib.micv_sift_descriptors_u8_host(c.handle, B.ptr(img), rows, cols, _pitch8(img), kp.ctypes.data, n, desc.ctypes.data, 512))
+    return desc[:n]
+
+
+def computeDescriptors8Batch(imgs, keypoints, count=None, ctx=None):
+    """computeDescriptors8 on a [batch, rows, cols] uint8 device tensor of any batch and row stride with [batch, cap, 4]
+    keypoints and a [batch] int64 device count (None: every row), one call (micv_sift_descriptors_u8_batch_dev): what
+    cornersFromImage8Batch(keypointSize=...) returns goes straight in.  -> [batch, cap, 128] float32; element i holds the
+    bytes of computeDescriptors8(imgs[i], keypoints[i], count[i:i+1])."""
+    if not B.is_dev(imgs) or not imgs.is_cuda or imgs.dim() != 3 or imgs.dtype != B.torch.uint8 or imgs.stride(2) != 1:
+        raise ValueError("imgs: need a [batch, rows, cols] uint8 device tensor with unit column stride")
+    if imgs.shape[0] < 1:
+        raise ValueError("imgs: the batch is empty")
+    import torch
+    batch, rows, cols = imgs.shape
+    if not (B.is_dev(keypoints) and keypoints.is_cuda and keypoints.device == imgs.device and keypoints.dim() == 3
+            and keypoints.shape[0] == batch and keypoints.shape[2] == 4):
+        raise ValueError("keypoints: need a [batch, cap, 4] CUDA tensor on imgs' device")
+    kp = keypoints.to(torch.float32).contiguous()
+    cap = int(kp.shape[1])
+    if count is not None and not (B.is_dev(count) and count.is_cuda and count.device == imgs.device and count.dtype == torch.int64
+                                  and count.numel() == batch and count.is_contiguous()):
+        raise ValueError("count: a contiguous [batch] int64 CUDA tensor on imgs' device expected")
+    desc = torch.zeros((batch, cap, 128), dtype=torch.float32, device=imgs.device)
+    check(lib.micv_sift_descriptors_u8_batch_dev(_ctx_for(imgs, ctx).handle, imgs.data_ptr(), imgs.stride(0) if batch > 1 else 0, batch, rows,
+                                                 cols, _pitch8(imgs), kp.data_ptr(), cap, count.data_ptr() if count is not None else None,
+                                                 desc.data_ptr(), cap * 512, 512, B.stream_of(imgs)))
+    return desc

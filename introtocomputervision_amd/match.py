@@ -47,6 +47,30 @@ def knnMatch2(query, train, ctx=None):
     return idx, dist
 
 
+def knnMatch2Counted(query, train, query_count, train_count, ctx=None):
+    """knnMatch2 on CUDA tensors whose lengths are device words (micv_bf_knn2_counted_dev): query [nq_cap, dim] and train
+    [nt_cap, dim] float32, query_count / train_count 1-element int64 CUDA tensors, clamped to [0, cap] on the device.
+    -> (idx [nq_cap, 2], dist [nq_cap, 2]): rows below the query count as knnMatch2(query[:nq], train[:nt]), the rows
+    past it {-1, -1} / {+inf, +inf}, which ratioTest never keeps.  Nothing is read back."""
+    import torch
+    for t, n in ((query, "query"), (train, "train")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 2 and t.dtype == torch.float32
+                and t.stride(1) == 1):
+            raise ValueError(f"{n}: need a 2-D float32 CUDA tensor with unit column stride")
+    if query.shape[1] != train.shape[1]:
+        raise ValueError("descriptor dimensions differ")
+    for t, n in ((query_count, "query_count"), (train_count, "train_count")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.numel() == 1 and t.device == query.device):
+            raise ValueError(f"{n}: need a 1-element int64 CUDA tensor on query's device")
+    nq, dim = query.shape
+    idx = torch.empty((nq, 2), dtype=torch.int32, device=query.device)
+    dist = torch.empty((nq, 2), dtype=torch.float32, device=query.device)
+    check(lib.micv_bf_knn2_counted_dev(_ctx_for(query, ctx).handle, query.data_ptr(), nq, query.stride(0) * 4, query_count.data_ptr(),
+                                       train.data_ptr(), train.shape[0], train.stride(0) * 4, train_count.data_ptr(), dim,
+                                       idx.data_ptr(), dist.data_ptr(), torch.cuda.current_stream(query.device).cuda_stream))
+    return idx, dist
+
+
 def ratioTest(idx, dist, ratio=0.75, ctx=None):
     """Good matches: (matches [n, 2] int32 = (queryIdx, trainIdx), distances [n]) in query order."""
     import numpy as np

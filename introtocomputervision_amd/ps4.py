@@ -290,13 +290,9 @@ def runProblem2(img_a, img_b, params, capacity=4096, ratio=0.75, ctx=None):
     return out
 
 
-def runProblem3(img_a, img_b, params, whichTransform, ransacReprojThresh=3, maxIters=2000, minConsensusRatio=0.75, seed=0,
-                capacity=4096, ctx=None):
-    """runProblem2's chain, then ransacHelper on the device (ransac.solve_matches and the consensus lines of its inlier
-    mask) and, for a similarity or affine transform, the registration tail (warp.registerBlend).  Adds "transforms",
-    "inlier_mask", "stats", "consensus_panel" and "blended" (None for a translation) to runProblem2's dict."""
+def _ransac_tail(out, img_a, img_b, whichTransform, ransacReprojThresh, maxIters, minConsensusRatio, seed, ctx):
+    """ransacHelper and the registration tail on the dict of runProblem2 / runProblem2_8 (both runProblem3 forms end here)."""
     from . import ransac, warp
-    out = runProblem2(img_a, img_b, params, capacity, ctx=ctx)
     tr, mask, st = ransac.solve_matches(out["kp_a"], out["kp_b"], out["matches"], out["match_count"], whichTransform,
                                         ransacReprojThresh, maxIters, minConsensusRatio, seed, ctx=ctx)
     _, panel = matchPanels(img_a, img_b, out["kp_a"], out["kp_b"], out["matches"], match_count=out["match_count"], mask=mask,
@@ -304,3 +300,62 @@ def runProblem3(img_a, img_b, params, whichTransform, ransacReprojThresh=3, maxI
     blended = warp.registerBlend(img_a, img_b, tr[0], ctx=ctx) if ransac._type(whichTransform) != 1 else None
     out.update(transforms=tr, inlier_mask=mask, stats=st, consensus_panel=panel, blended=blended)
     return out
+
+
+def runProblem2_8(img_a, img_b, params, capacity=4096, ratio=0.75, ctx=None):
+    """runProblem2 on the two 8-bit pictures themselves, every list length a device word from the corners to the panels:
+    harris.cornersFromImage8Batch with keypoints and without planes (two single calls when the pictures differ in size),
+    harris.computeDescriptors8Batch, match.knnMatch2Counted, the ratio filter and the panels.  No float image, no gradient
+    plane, no masking of rows past a count, nothing read back.  "a" / "b" are the corner dicts ("locs", "count",
+    "keypoints"); "kp_a", "kp_b" (rows below the counts), "matches", "match_count" and the panels hold runProblem2's bytes."""
+    import torch
+    from . import harris
+    from .match import knnMatch2Counted
+    if not (B.is_dev(img_a) and B.is_dev(img_b)):
+        raise ValueError("runProblem2_8: CUDA tensors expected (the host entry points serve the single steps)")
+    for name, img in (("img_a", img_a), ("img_b", img_b)):
+        if img.dtype != torch.uint8 or img.dim() != 2:
+            raise ValueError(f"{name}: a [rows, cols] uint8 tensor expected")
+    hp = dict(sobelSize=params["sobel_kernel_size"], windowSize=params["window_size"], gaussianSigma=params["gaussian_sigma"],
+              harrisScore=params["alpha"], threshold=params["response_threshold"], minDistance=params["min_distance"], capacity=capacity,
+              ctx=ctx, want_gradients=False, keypointSize=SIFT_WINDOW_SIZE)
+    out = {}
+    if tuple(img_a.shape) == tuple(img_b.shape):
+        pair = torch.stack((img_a, img_b))
+        d = harris.cornersFromImage8Batch(pair, **hp)
+        desc = harris.computeDescriptors8Batch(pair, d["keypoints"], d["count"], ctx=ctx)
+        for i, key in enumerate("ab"):
+            out[key] = {"locs": d["locs"][i], "count": d["count"][i:i + 1], "keypoints": d["keypoints"][i]}
+        descs = [desc[0], desc[1]]
+    else:
+        descs = []
+        for key, img in (("a", img_a), ("b", img_b)):
+            d = out[key] = harris.cornersFromImage8(img, lazy=True, **hp)
+            descs.append(harris.computeDescriptors8(img, d["keypoints"], d["count"], ctx=ctx))
+    kps = [out["a"]["keypoints"], out["b"]["keypoints"]]
+    idx, dist = knnMatch2Counted(descs[0], descs[1], out["a"]["count"], out["b"]["count"], ctx=ctx)
+    nq = idx.shape[0]
+    matches = torch.zeros((nq, 2), dtype=torch.int32, device=img_a.device)
+    distances = torch.empty((nq,), dtype=torch.float32, device=img_a.device)
+    mcount = torch.zeros((1,), dtype=torch.int64, device=img_a.device)
+    check(lib.micv_bf_ratio_filter_dev(_ctx_for(idx, ctx).handle, idx.data_ptr(), dist.data_ptr(), nq, float(ratio), matches.data_ptr(),
+                                       distances.data_ptr(), nq, mcount.data_ptr(), B.stream_of(idx)))
+    kpanel, mpanel = matchPanels(img_a, img_b, kps[0], kps[1], matches, out["a"]["count"], out["b"]["count"], mcount, ctx=ctx)
+    out.update(kp_a=kps[0], kp_b=kps[1], matches=matches, match_count=mcount, keypoints_panel=kpanel, matches_panel=mpanel)
+    return out
+
+
+def runProblem3_8(img_a, img_b, params, whichTransform, ransacReprojThresh=3, maxIters=2000, minConsensusRatio=0.75, seed=0,
+                  capacity=4096, ctx=None):
+    """runProblem3 on runProblem2_8's chain: the same "transforms", "inlier_mask", "stats", "consensus_panel" and "blended"."""
+    return _ransac_tail(runProblem2_8(img_a, img_b, params, capacity, ctx=ctx), img_a, img_b, whichTransform, ransacReprojThresh, maxIters,
+                        minConsensusRatio, seed, ctx)
+
+
+def runProblem3(img_a, img_b, params, whichTransform, ransacReprojThresh=3, maxIters=2000, minConsensusRatio=0.75, seed=0,
+                capacity=4096, ctx=None):
+    """runProblem2's chain, then ransacHelper on the device (ransac.solve_matches and the consensus lines of its inlier
+    mask) and, for a similarity or affine transform, the registration tail (warp.registerBlend).  Adds "transforms",
+    "inlier_mask", "stats", "consensus_panel" and "blended" (None for a translation) to runProblem2's dict."""
+    return _ransac_tail(runProblem2(img_a, img_b, params, capacity, ctx=ctx), img_a, img_b, whichTransform, ransacReprojThresh, maxIters,
+                        minConsensusRatio, seed, ctx)

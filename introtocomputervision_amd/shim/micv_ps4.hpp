@@ -368,6 +368,19 @@ inline void harrisCorners8(FeaturesContainer &conf) {
     for (int64_t i = 0; i < count; i++) conf.cornerLocs.emplace_back(locs[2 * i], locs[2 * i + 1]);
 }
 
+// The descriptor step of siftHelper (Solution.cpp:166-169) on the 8-bit picture itself: desc = keypoints.size() x 128 F32
+// from img8 (CV_8UC1; an ROI with a foreign step is fine) with ONE micv_sift_descriptors_u8_host call -- 1 B per pixel goes
+// up and no gradient Mat is needed.  Same bytes as sift::computeDescriptors on harris::getGradients(img8 as F32, 3).
+inline void siftDescriptors8(const Mat &img8, const std::vector<KeyPoint> &keypoints, Mat &desc) {
+    if (img8.type() != micv::CV_8UC1) throw std::invalid_argument("siftDescriptors8: CV_8UC1 expected");
+    const std::vector<float> kp = flat_keypoints(keypoints);
+    Mat out(static_cast<int>(keypoints.size()), 128, micv_shim::F32);
+    if (!keypoints.empty())
+        micv_shim::check(micv_sift_descriptors_u8_host(micv_shim::context(), img8.ptr<uint8_t>(), img8.rows, img8.cols, img8.step, kp.data(),
+                                                       static_cast<int64_t>(keypoints.size()), out.ptr<float>(), out.step));
+    desc = out;
+}
+
 // siftHelper's computing steps (Solution.cpp:141-144, :166-186), shared by the two forms below
 inline void siftCompute(FeaturesContainer &img1, FeaturesContainer &img2) {
     constexpr size_t SIFT_WINDOW_SIZE = 10;
