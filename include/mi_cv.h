@@ -809,6 +809,33 @@ int micv_bf_ratio_filter_dev(micv_ctx *ctx, const int32_t *idx2, const float *di
 int micv_bf_ratio_filter_host(micv_ctx *ctx, const int32_t *idx2, const float *dist2, int nq,
                               double ratio, int32_t *matches_qt, float *distances, int64_t cap,
                               int64_t *count);
+/* Matcher and ratio test on a BATCH OF PAIRS of one descriptor batch, two launches for the whole batch, nothing read back.
+ * desc holds `images` lists of `cap` rows x dim f32 (row r of image i at desc + i*dimage_stride + r*dstride, bytes; what
+ * micv_sift_descriptors_u8_batch_dev leaves), count [images] their DEVICE lengths (clamped to [0, cap]; NULL: all cap
+ * rows), pairs [npairs][2] int32 on the DEVICE: (query image, train image).  Element p of every output holds the bytes of
+ * micv_bf_knn2_counted_dev(query = image pairs[p][0], train = image pairs[p][1], their count words, nq_cap = nt_cap = cap)
+ * followed by micv_bf_ratio_filter_dev over cap rows with capacity mcap:
+ *   idx2, dist2 [npairs][cap][2]  optional, both or neither;
+ *   match_count [npairs]          the total kept, which may exceed mcap;
+ *   matches_qt [npairs][mcap][2], distances [npairs][mcap]: rows < min(match_count[p], mcap); the rows at and past that
+ *                                 are not written (mcap == 0: counts only, both may be NULL).
+ * A pair may name one image twice, pairs may repeat, (a, b) and (b, a) may both appear.  A pair index outside [0, images)
+ * behaves as two empty lists: idx2 / dist2 rows {-1, -1} / {+inf, +inf}, match_count[p] = 0.
+ * Slicing of the train set: a launch has S = min(ceil(2048 / (ceil(cap / 64) * npairs)), ceil(cap / 128)) slices (at
+ * least 1, and no more than keep ONE pair's partial lists within the bound below), and a pair's slice holds ceil(ceil(nt / 128) / S) * 128 rows of ITS clamped train count nt, read on the
+ * device -- a short list spreads over as many workgroups as it has 128-row passes, not over slice 0 alone.  The top-2
+ * order (distance, index) is total, so no byte depends on S.  The partial top-2 lists (16 * S * cap bytes per pair) are
+ * bounded at 64 MiB per launch: larger batches go in pieces on the stream.  One workgroup per pair folds the slices,
+ * applies the ratio test and compacts in query order; no workgroup waits for another, and neither compact_state nor the
+ * context's status words are touched.
+ * Errors (MICV_EINVAL, before anything is enqueued): a null ctx / desc / pairs / match_count, one of idx2 / dist2
+ * without the other, images < 1, npairs outside 1 .. 65535, cap < 1, dim < 1, mcap < 0 or mcap > 0 without matches_qt
+ * and distances, a dstride that is no multiple of 4 or below dim * 4, a dimage_stride that is no multiple of 4 or below
+ * (cap - 1) * dstride + dim * 4. */
+int micv_bf_match_pairs_dev(micv_ctx *ctx, const float *desc, int images, size_t dimage_stride, int cap, size_t dstride,
+                            const int64_t *count, int dim, const int32_t *pairs, int npairs, double ratio, int32_t *idx2,
+                            float *dist2, int32_t *matches_qt, float *distances, int64_t mcap, int64_t *match_count,
+                            micv_stream stream);
 
 /* ------------------------------------------------------------- ps4: RANSAC --------- */
 
@@ -877,6 +904,24 @@ int micv_ransac_solve_matches_dev(micv_ctx *ctx, const float *kp_a, int64_t na, 
                                   int64_t cap, uint64_t seed, int iters, int type, int thresh,
                                   double min_ratio, float *transforms, uint8_t *inlier_mask,
                                   int32_t *stats, micv_stream stream);
+/* The same solve on a BATCH OF PAIRS: one memset, one gather over (match, pair), one score launch over (hypothesis
+ * chunk, pair) and one finalize launch with a workgroup per pair, whatever npairs is.  kp_xysa holds `images` lists of kcap
+ * keypoint rows (image i at kp_xysa + i*kimage_stride bytes), pairs [npairs][2] int32 on the DEVICE as for
+ * micv_bf_match_pairs_dev, whose matches_qt [npairs][mcap][2] and match_count [npairs] go straight in.  Element p of
+ * transforms [npairs][2][6], inlier_mask [npairs][mcap] and stats [npairs][3] holds the bytes of
+ * micv_ransac_solve_matches_dev(kp_a = image pairs[p][0], na = kcap, kp_b = image pairs[p][1], nb = kcap, pair p's
+ * matches and count word, cap = mcap, seed_p) with
+ *     seed_p = splitmix64(seed + p)          (64-bit addition, wrapping; splitmix64 as written above).
+ * The sampler xors the seed with the draw's counter word, so seed + p alone would hand pair p + 1 the draws of pair p
+ * under another counter; the hash keeps adjacent pairs' draws apart.  Control words, stop words and count rows are per
+ * pair: n < k gives that pair {0, -1, 0}, a match index outside the lists gives it {-1, -1, 0} and zero outputs, and its
+ * neighbours are not affected.  A pair index outside [0, images) gives {-1, -1, 0} and zero outputs.
+ * Errors: those of micv_ransac_solve_matches_dev, images < 1, npairs outside 1 .. 65535, a kimage_stride that is no
+ * multiple of 4 or below kcap * 16. */
+int micv_ransac_solve_pairs_dev(micv_ctx *ctx, const float *kp_xysa, int images, size_t kimage_stride, int64_t kcap,
+                                const int32_t *pairs, int npairs, const int32_t *matches_qt, const int64_t *match_count,
+                                int64_t mcap, uint64_t seed, int iters, int type, int thresh, double min_ratio,
+                                float *transforms, uint8_t *inlier_mask, int32_t *stats, micv_stream stream);
 
 /* -------------------------------------------------------- ps4: registration --------- */
 

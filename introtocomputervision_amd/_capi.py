@@ -226,6 +226,7 @@ SIGNATURES = {
     "micv_bf_knn2_dev": (i32, [vp, vp, i32, sz, vp, i32, sz, i32, vp, vp, vp]),
     "micv_bf_knn2_counted_dev": (i32, [vp, vp, i32, sz, vp, vp, i32, sz, vp, i32, vp, vp, vp]),
     "micv_bf_ratio_filter_dev": (i32, [vp, vp, vp, i32, f64, vp, vp, i64, vp, vp]),
+    "micv_bf_match_pairs_dev": (i32, [vp, vp, i32, sz, i32, sz, vp, i32, vp, i32, f64, vp, vp, vp, vp, i64, vp, vp]),
     # ps4 RANSAC
     "micv_ransac_rng_create": (i32, [vp, i32, C.POINTER(vp)]),
     "micv_ransac_rng_destroy": (None, [vp]),
@@ -236,6 +237,8 @@ SIGNATURES = {
     "micv_ransac_solve_host": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, f64, vp, vp, vp]),
     "micv_ransac_solve_matches_dev": (i32, [vp, vp, i64, vp, i64, vp, vp, i64, C.c_uint64, i32, i32, i32, f64,
                                             vp, vp, vp, vp]),
+    "micv_ransac_solve_pairs_dev": (i32, [vp, vp, i32, sz, i64, vp, i32, vp, vp, i64, C.c_uint64, i32, i32, i32, f64,
+                                          vp, vp, vp, vp]),
     # ps4 registration
     "micv_invert_affine_dev": (i32, [vp, vp, i32, vp, vp]),
     "micv_invert_affine_host": (i32, [vp, vp, i32, vp]),

@@ -9,6 +9,8 @@
 // through LDS in tiles of 64 rows, and every thread carries 16 independent chains (one query x 16
 // train rows), reading its query element from a padded LDS image and the train element as a
 // wave-wide broadcast.
+#include <algorithm>
+
 #include "compact.hpp"
 #include "kernels.hpp"
 
@@ -48,25 +50,14 @@ __device__ __forceinline__ int bf_clamped_count(const int64_t *count, int cap) {
     return c < 0 ? 0 : (c < cap ? (int)c : cap);
 }
 
-template <bool COUNTED>
-__global__ __launch_bounds__(256) void bf_knn2_kernel(const float *__restrict__ query, int nq_cap,
-                                                       int qstride, const float *__restrict__ train,
-                                                       int nt_cap, int tstride, int dim, int slice_rows,
-                                                       int32_t *__restrict__ part_i,
-                                                       float *__restrict__ part_d, int vec_ok,
-                                                       const int64_t *__restrict__ nq_count,
-                                                       const int64_t *__restrict__ nt_count) {
-    int nq = nq_cap, nt = nt_cap;
-    if constexpr (COUNTED) {
-        nq = bf_clamped_count(nq_count, nq_cap);
-        nt = bf_clamped_count(nt_count, nt_cap);
-        if ((int)blockIdx.x * kQT >= nq) return;
-    }
+// The tile body of every search kernel: queries [q0, q0 + 64) of `query` (rows at and past nq are not read) against train
+// rows [ts0, ts1).  Returns true in the threads that hold a query's folded top-2 (tid < 64, q0 + tid < nq), `m` is that list.
+__device__ __forceinline__ bool bf_tile_search(const float *__restrict__ query, int q0, int nq, int qstride,
+                                               const float *__restrict__ train, int ts0, int ts1, int tstride, int dim,
+                                               int vec_ok, Top2 &m) {
     __shared__ __attribute__((aligned(16))) float Qt[kDC][kQT];
     __shared__ __attribute__((aligned(16))) float Tt[kDC][kTT];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int q0 = blockIdx.x * kQT;
-    const int ts0 = blockIdx.y * slice_rows, ts1 = ts0 + slice_rows < nt ? ts0 + slice_rows : nt;
     Top2 best[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) best[i].init();
@@ -165,13 +156,33 @@ __global__ __launch_bounds__(256) void bf_knn2_kernel(const float *__restrict__ 
         mi[ty][4 * tx + i][0] = best[i].i0; mi[ty][4 * tx + i][1] = best[i].i1;
     }
     __syncthreads();
-    if (tid < kQT && q0 + tid < nq) {
-        Top2 m;
-        m.init();
-        for (int g = 0; g < 16; g++)
-            for (int sidx = 0; sidx < 2; sidx++)
-                if (mi[g][tid][sidx] >= 0) m.push(md[g][tid][sidx], mi[g][tid][sidx]);
-        const size_t o = ((size_t)blockIdx.y * nq_cap + q0 + tid) * 2;
+    if (!(tid < kQT && q0 + tid < nq)) return false;
+    m.init();
+    for (int g = 0; g < 16; g++)
+        for (int sidx = 0; sidx < 2; sidx++)
+            if (mi[g][tid][sidx] >= 0) m.push(md[g][tid][sidx], mi[g][tid][sidx]);
+    return true;
+}
+
+template <bool COUNTED>
+__global__ __launch_bounds__(256) void bf_knn2_kernel(const float *__restrict__ query, int nq_cap,
+                                                       int qstride, const float *__restrict__ train,
+                                                       int nt_cap, int tstride, int dim, int slice_rows,
+                                                       int32_t *__restrict__ part_i,
+                                                       float *__restrict__ part_d, int vec_ok,
+                                                       const int64_t *__restrict__ nq_count,
+                                                       const int64_t *__restrict__ nt_count) {
+    int nq = nq_cap, nt = nt_cap;
+    if constexpr (COUNTED) {
+        nq = bf_clamped_count(nq_count, nq_cap);
+        nt = bf_clamped_count(nt_count, nt_cap);
+        if ((int)blockIdx.x * kQT >= nq) return;
+    }
+    const int q0 = blockIdx.x * kQT;
+    const int ts0 = blockIdx.y * slice_rows, ts1 = ts0 + slice_rows < nt ? ts0 + slice_rows : nt;
+    Top2 m;
+    if (bf_tile_search(query, q0, nq, qstride, train, ts0, ts1, tstride, dim, vec_ok, m)) {
+        const size_t o = ((size_t)blockIdx.y * nq_cap + q0 + threadIdx.x) * 2;
         part_i[o] = m.i0; part_i[o + 1] = m.i1;
         part_d[o] = m.d0; part_d[o + 1] = m.d1;
     }
@@ -223,6 +234,123 @@ __global__ void bf_emit_kernel(const int32_t *__restrict__ sel, const int64_t *_
         matches[2 * i + 1] = idx2[2 * q];
         distances[i] = dist2[2 * q];
     }
+}
+
+// ---- a batch of pairs (micv_bf_match_pairs_dev) ----
+// Two launches for a whole piece of the batch, the pair a grid dimension of both; neither waits for the host.
+//   bf_knn2_pairs_kernel    the tile body above on (64-query block, train slice, pair)
+//   bf_finish_pairs_kernel  ONE workgroup per pair: folds the slices, takes the roots, writes idx2 / dist2, applies the
+//                           ratio test and compacts in query order with wave ballots and a carried base -- no workgroup
+//                           waits for another, no status words, no compact_state slot (harris_list_kernel's pattern)
+// SLICING.  The launch has S = gridDim.y slices; how many train rows a slice holds is decided ON THE DEVICE from the
+// pair's clamped train count nt:  slice_rows = ceil(ceil(nt / 128) / S) * 128, slice s = rows [s * slice_rows,
+// min((s + 1) * slice_rows, nt)), so ceil(nt / slice_rows) slices hold rows and a short list still spreads over as
+// many workgroups as it has 128-row passes.  Workgroups of the other slices, and of query blocks at and past the query
+// count, leave before any barrier and write nothing; the finish kernel derives the same numbers and reads only what was
+// written.  The top-2 order (distance, index) is total, so no output depends on S.
+constexpr size_t kPairsScratchBytes = size_t(64) << 20;  // partial lists of one piece (mi_cv.h)
+constexpr int kPairsWantWgs = 2048;                      // S: enough slices for this many workgroups, at most cap / 128
+constexpr int kFinishThreads = 1024;
+
+struct alignas(16) PairPart {  // one query's top-2 within one slice
+    int i0, i1;
+    float d0, d1;
+};
+
+__device__ __forceinline__ int bf_pair_slice_rows(int nt, int slices) {
+    const int passes = (nt + kTT - 1) / kTT;
+    return (passes + slices - 1) / slices * kTT;
+}
+
+// The lists of pair p: false when an image index lies outside [0, images) (two empty lists).
+__device__ __forceinline__ bool bf_pair_lists(const int32_t *__restrict__ pairs, int p, int images, int cap,
+                                              const int64_t *__restrict__ count, int &a, int &b, int &nq, int &nt) {
+    a = pairs[2 * (size_t)p];
+    b = pairs[2 * (size_t)p + 1];
+    nq = nt = 0;
+    if ((unsigned)a >= (unsigned)images || (unsigned)b >= (unsigned)images) return false;
+    nq = count ? bf_clamped_count(count + a, cap) : cap;
+    nt = count ? bf_clamped_count(count + b, cap) : cap;
+    return true;
+}
+
+// (the two list pointers are computed here, not kernel arguments the compiler can load again, and two scalar words spill
+// into a VGPR lane: without the occupancy attribute that lane is the 129th VGPR and the fourth workgroup per CU is lost)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void bf_knn2_pairs_kernel(const float *__restrict__ desc, int images, size_t image_floats,
+                                                             int cap, int dstride, const int64_t *__restrict__ count, int dim,
+                                                             const int32_t *__restrict__ pairs, int pair0,
+                                                             PairPart *__restrict__ part, int vec_ok) {
+    int a, b, nq, nt;
+    if (!bf_pair_lists(pairs, pair0 + (int)blockIdx.z, images, cap, count, a, b, nq, nt)) return;
+    const int q0 = blockIdx.x * kQT;
+    if (q0 >= nq) return;
+    part += ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * cap + q0;  // (now: fewer words live across the tile body)
+    const int slice_rows = bf_pair_slice_rows(nt, gridDim.y);
+    const int ts0 = blockIdx.y * slice_rows, ts1 = ts0 + slice_rows < nt ? ts0 + slice_rows : nt;  // (cap <= 2^30: no overflow)
+    if (ts0 >= nt) return;
+    Top2 m;
+    if (bf_tile_search(desc + a * image_floats, q0, nq, dstride, desc + b * image_floats, ts0, ts1, dstride, dim, vec_ok, m)) {
+        part[threadIdx.x] = PairPart{m.i0, m.i1, m.d0, m.d1};
+    }
+}
+
+__global__ __launch_bounds__(kFinishThreads) void bf_finish_pairs_kernel(const PairPart *__restrict__ part, int images, int cap,
+                                                                          const int64_t *__restrict__ count,
+                                                                          const int32_t *__restrict__ pairs, int pair0, int slices,
+                                                                          double ratio, int32_t *__restrict__ idx2,
+                                                                          float *__restrict__ dist2, int32_t *__restrict__ matches,
+                                                                          float *__restrict__ distances, int64_t mcap,
+                                                                          int64_t *__restrict__ match_count) {
+    __shared__ unsigned wave_total[kFinishThreads / 64];
+    const size_t p = (size_t)pair0 + blockIdx.x;
+    int a, b, nq, nt;
+    bf_pair_lists(pairs, (int)p, images, cap, count, a, b, nq, nt);
+    const int slice_rows = bf_pair_slice_rows(nt, slices);
+    const int used = nt > 0 ? (nt + slice_rows - 1) / slice_rows : 0;
+    const size_t part0 = (size_t)blockIdx.x * slices * cap;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int32_t *I = idx2 ? idx2 + p * (size_t)cap * 2 : nullptr;
+    float *D = dist2 ? dist2 + p * (size_t)cap * 2 : nullptr;
+    int32_t *M = matches + p * (size_t)mcap * 2;  // (never dereferenced when mcap == 0)
+    float *E = distances + p * (size_t)mcap;
+    int64_t base = 0;
+    for (int q0 = 0; q0 < cap; q0 += kFinishThreads) {
+        const int q = q0 + (int)threadIdx.x;
+        Top2 m;
+        m.init();
+        if (q < nq)
+            for (int s = 0; s < used; s++) {
+                const PairPart r = part[part0 + (size_t)s * cap + q];
+                if (r.i0 >= 0) m.push(r.d0, r.i0);
+                if (r.i1 >= 0) m.push(r.d1, r.i1);
+            }
+        const float d0 = sqrtf(m.d0), d1 = sqrtf(m.d1);
+        if (q < cap && I) {
+            I[2 * (size_t)q] = m.i0; I[2 * (size_t)q + 1] = m.i1;
+            D[2 * (size_t)q] = d0; D[2 * (size_t)q + 1] = d1;
+        }
+        const bool keep = q < cap && RatioPred{nullptr, ratio}.test(q, make_float2(d0, d1));
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) wave_total[wave] = __popcll(bal);
+        __syncthreads();
+        unsigned before = 0, total = 0;
+#pragma unroll
+        for (int j = 0; j < kFinishThreads / 64; j++) {
+            const unsigned t = wave_total[j];
+            before += j < wave ? t : 0u;
+            total += t;
+        }
+        __syncthreads();  // wave_total is written again in the next pass
+        if (keep) {
+            const int64_t pos = base + before + __popcll(bal & ((1ull << lane) - 1));
+            if (pos < mcap) {
+                M[2 * pos] = q; M[2 * pos + 1] = m.i0;
+                E[pos] = d0;
+            }
+        }
+        base += total;
+    }
+    if (threadIdx.x == 0) match_count[p] = base;
 }
 
 }  // namespace micv
@@ -285,6 +413,42 @@ int micv_bf_knn2_counted_dev(micv_ctx *ctx, const float *query, int nq_cap, size
     MICV_REQUIRE(nq_cap > 0 && nt_cap > 0 && dim > 0, "micv_bf_knn2_counted: need nq_cap > 0, nt_cap > 0, dim > 0");
     MICV_REQUIRE(stride_ok(qstride, dim, 4) && stride_ok(tstride, dim, 4), "micv_bf_knn2_counted: bad stride");
     return bf_knn2_run(ctx, query, nq_cap, qstride, nq_count, train, nt_cap, tstride, nt_count, dim, idx2, dist2, stream);
+}
+
+int micv_bf_match_pairs_dev(micv_ctx *ctx, const float *desc, int images, size_t dimage_stride, int cap, size_t dstride,
+                            const int64_t *count, int dim, const int32_t *pairs, int npairs, double ratio, int32_t *idx2,
+                            float *dist2, int32_t *matches_qt, float *distances, int64_t mcap, int64_t *match_count,
+                            micv_stream stream) {
+    MICV_REQUIRE(ctx && desc && pairs && match_count, "micv_bf_match_pairs: null argument");
+    MICV_REQUIRE(!idx2 == !dist2, "micv_bf_match_pairs: idx2 and dist2 go together (both or neither)");
+    MICV_REQUIRE(images >= 1 && cap >= 1 && dim >= 1, "micv_bf_match_pairs: need images >= 1, cap >= 1, dim >= 1");
+    MICV_REQUIRE(npairs >= 1 && npairs <= 65535, "micv_bf_match_pairs: npairs %d outside 1 .. 65535", npairs);
+    MICV_REQUIRE(mcap >= 0 && (mcap == 0 || (matches_qt && distances)), "micv_bf_match_pairs: bad mcap / outputs");
+    MICV_REQUIRE(stride_ok(dstride, dim, 4), "micv_bf_match_pairs: bad stride");
+    MICV_REQUIRE(dimage_stride % 4 == 0 && dimage_stride >= (size_t)(cap - 1) * dstride + (size_t)dim * 4,
+                 "micv_bf_match_pairs: dimage_stride %zu is no multiple of 4 or below one image's rows", dimage_stride);
+    MICV_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // S slices (the rule at bf_knn2_pairs_kernel), then as many pairs per launch as keep the partial lists in bound
+    const int qblocks = (int)cdiv(cap, kQT), passes = (int)cdiv(cap, kTT);
+    const size_t pair_bytes = (size_t)cap * sizeof(PairPart);  // one slice of one pair
+    int64_t slices = std::min<int64_t>(((int64_t)kPairsWantWgs + (int64_t)qblocks * npairs - 1) / ((int64_t)qblocks * npairs), passes);
+    slices = std::max<int64_t>(1, std::min<int64_t>(slices, (int64_t)(kPairsScratchBytes / pair_bytes)));
+    const int piece = (int)std::max<size_t>(1, std::min<size_t>((size_t)npairs, kPairsScratchBytes / (pair_bytes * slices)));
+    void *scratch;
+    MICV_TRY(ctx->reserve((size_t)piece * slices * pair_bytes, &scratch));
+    PairPart *part = static_cast<PairPart *>(scratch);
+    const int vec_ok = ((reinterpret_cast<uintptr_t>(desc) | dstride | dimage_stride) & 15) == 0 && (dim & 3) == 0;
+    for (int p0 = 0; p0 < npairs; p0 += piece) {  // (pieces reuse the partial lists: stream order keeps them apart)
+        const int np = std::min(piece, npairs - p0);
+        bf_knn2_pairs_kernel<<<dim3(qblocks, (unsigned)slices, np), 256, 0, s>>>(desc, images, dimage_stride / 4, cap, (int)(dstride / 4),
+                                                                                 count, dim, pairs, p0, part, vec_ok);
+        MICV_LAUNCH_CHECK();
+        bf_finish_pairs_kernel<<<np, kFinishThreads, 0, s>>>(part, images, cap, count, pairs, p0, (int)slices, ratio, idx2,
+                                                             dist2, matches_qt, distances, mcap, match_count);
+        MICV_LAUNCH_CHECK();
+    }
+    return MICV_OK;
 }
 
 int micv_bf_ratio_filter_dev(micv_ctx *ctx, const int32_t *idx2, const float *dist2, int nq,

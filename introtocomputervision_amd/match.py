@@ -96,3 +96,58 @@ def ratioTest(idx, dist, ratio=0.75, ctx=None):
                                        cnt.data_ptr(), torch.cuda.current_stream(idx.device).cuda_stream))
     n = int(cnt.item())
     return matches[:n], distances[:n]
+
+
+def pairList(pairs, images, device):
+    """The (query image, train image) list of matchPairs / ransac.solve_pairs as an [npairs, 2] int32 CUDA tensor.  A Python
+    list is range-checked here (ValueError); a CUDA tensor goes through as it is -- the kernels treat an index outside
+    [0, images) as two empty lists."""
+    import torch
+    if isinstance(pairs, torch.Tensor):
+        if not (pairs.is_cuda and pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.is_contiguous()
+                and pairs.device == device):
+            raise ValueError("pairs: need a contiguous [npairs, 2] int32 CUDA tensor on the data's device")
+        t = pairs
+    else:
+        rows = [(int(a), int(b)) for a, b in pairs]
+        for a, b in rows:
+            if not (0 <= a < images and 0 <= b < images):
+                raise ValueError(f"pairs: ({a}, {b}) names an image outside 0 .. {images - 1}")
+        t = torch.tensor(rows, dtype=torch.int32).reshape(-1, 2).to(device)
+    if not 1 <= t.shape[0] <= 65535:
+        raise ValueError("pairs: need 1 .. 65535 pairs")
+    return t
+
+
+def matchPairs(desc, count, pairs, ratio=0.75, capacity=None, want_knn=False, ctx=None):
+    """knnMatch2Counted + the ratio test on a batch of pairs in two launches (micv_bf_match_pairs_dev).  desc [images, cap,
+    dim] float32 CUDA (any image and row stride), count [images] int64 CUDA or None (every row), pairs a list of (query
+    image, train image) or an [npairs, 2] int32 CUDA tensor (pairList).  -> (matches [npairs, capacity, 2] int32, distances
+    [npairs, capacity], match_count [npairs] int64), with want_knn also (idx [npairs, cap, 2], dist [npairs, cap, 2]).
+    Element p holds the bytes of the two single calls on pair p; match_count[p] is the total kept and may exceed
+    `capacity` (default cap); rows at and past min(match_count[p], capacity) are not written.  Nothing is read back."""
+    import torch
+    if not (isinstance(desc, torch.Tensor) and desc.is_cuda and desc.dim() == 3 and desc.dtype == torch.float32 and desc.stride(2) == 1):
+        raise ValueError("desc: need an [images, cap, dim] float32 CUDA tensor with unit column stride")
+    images, cap, dim = desc.shape
+    if images < 1 or cap < 1 or dim < 1:
+        raise ValueError("desc: empty")
+    if count is not None and not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype == torch.int64 and count.dim() == 1
+                                  and count.shape[0] == images and count.is_contiguous() and count.device == desc.device):
+        raise ValueError("count: need a contiguous [images] int64 CUDA tensor on desc's device")
+    pt = pairList(pairs, images, desc.device)
+    npairs = int(pt.shape[0])
+    mcap = cap if capacity is None else int(capacity)
+    dv = desc.device
+    matches = torch.empty((npairs, mcap, 2), dtype=torch.int32, device=dv)
+    distances = torch.empty((npairs, mcap), dtype=torch.float32, device=dv)
+    mcount = torch.empty((npairs,), dtype=torch.int64, device=dv)
+    idx = torch.empty((npairs, cap, 2), dtype=torch.int32, device=dv) if want_knn else None
+    dist = torch.empty((npairs, cap, 2), dtype=torch.float32, device=dv) if want_knn else None
+    check(lib.micv_bf_match_pairs_dev(_ctx_for(desc, ctx).handle, desc.data_ptr(), images, (desc.stride(0) if images > 1 else cap * desc.stride(1)) * 4,
+                                      cap, (desc.stride(1) if cap > 1 else dim) * 4, count.data_ptr() if count is not None else None, dim,
+                                      pt.data_ptr(), npairs, float(ratio), idx.data_ptr() if want_knn else None,
+                                      dist.data_ptr() if want_knn else None, matches.data_ptr() if mcap else None,
+                                      distances.data_ptr() if mcap else None, mcap, mcount.data_ptr(),
+                                      torch.cuda.current_stream(dv).cuda_stream))
+    return (matches, distances, mcount, idx, dist) if want_knn else (matches, distances, mcount)

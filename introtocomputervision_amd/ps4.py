@@ -359,3 +359,40 @@ def runProblem3(img_a, img_b, params, whichTransform, ransacReprojThresh=3, maxI
     "inlier_mask", "stats", "consensus_panel" and "blended" (None for a translation) to runProblem2's dict."""
     return _ransac_tail(runProblem2(img_a, img_b, params, capacity, ctx=ctx), img_a, img_b, whichTransform, ransacReprojThresh, maxIters,
                         minConsensusRatio, seed, ctx)
+
+
+def registerPairs8(imgs, pairs, params, whichTransform, ransacReprojThresh=3, maxIters=2000, minConsensusRatio=0.75, seed=0,
+                   capacity=4096, ratio=0.75, ctx=None):
+    """runProblem3_8's chain without its panels and its blend on a batch of pictures and a list of pairs of them, the number
+    of launches independent of both: harris.cornersFromImage8Batch (keypoints, no planes), harris.computeDescriptors8Batch,
+    match.matchPairs, ransac.solve_pairs and, for a similarity or affine type, warp.invertAffineTransform on row [0] of
+    every pair and warp.warpAffineBatch of the pairs' second pictures.  imgs: [B, rows, cols] uint8 on the device; pairs: a
+    list of (a, b), "chain" for (i, i + 1), "key" for (0, i), or an [npairs, 2] int32 CUDA tensor.  Returns the corner dict
+    ("locs", "count", "keypoints") plus "pairs", "matches", "match_count", "transforms" [npairs, 2, 2, 3], "inlier_mask",
+    "stats" and "warped" [npairs, rows, cols] (None for a translation).  Element p holds the bytes of runProblem3_8(imgs[a],
+    imgs[b], ..., seed=ransac.pairSeed(seed, p)).  Nothing is read back."""
+    import torch
+    from . import harris, match, ransac, warp
+    if not (B.is_dev(imgs) and imgs.is_cuda and imgs.dim() == 3 and imgs.dtype == torch.uint8):
+        raise ValueError("imgs: a [B, rows, cols] uint8 CUDA tensor expected")
+    nimg = int(imgs.shape[0])
+    if isinstance(pairs, str):
+        if pairs not in ("chain", "key") or nimg < 2:
+            raise ValueError('pairs: "chain" or "key" on at least two pictures, a list, or an int32 CUDA tensor')
+        pairs = [(i, i + 1) for i in range(nimg - 1)] if pairs == "chain" else [(0, i) for i in range(1, nimg)]
+    pt = match.pairList(pairs, nimg, imgs.device)
+    out = harris.cornersFromImage8Batch(imgs, sobelSize=params["sobel_kernel_size"], windowSize=params["window_size"],
+                                        gaussianSigma=params["gaussian_sigma"], harrisScore=params["alpha"],
+                                        threshold=params["response_threshold"], minDistance=params["min_distance"], capacity=capacity,
+                                        ctx=ctx, want_gradients=False, keypointSize=SIFT_WINDOW_SIZE)
+    desc = harris.computeDescriptors8Batch(imgs, out["keypoints"], out["count"], ctx=ctx)
+    matches, _, mcount = match.matchPairs(desc, out["count"], pt, ratio=ratio, ctx=ctx)
+    tr, mask, st = ransac.solve_pairs(out["keypoints"], pt, matches, mcount, whichTransform, ransacReprojThresh, maxIters,
+                                      minConsensusRatio, seed, ctx=ctx)
+    warped = None
+    if ransac._type(whichTransform) != 1:
+        inv = warp.invertAffineTransform(tr[:, 0].contiguous(), ctx=ctx)
+        second = imgs.index_select(0, pt[:, 1].to(torch.int64).clamp(0, nimg - 1))  # (a device gather: nothing read back)
+        warped = warp.warpAffineBatch(second, inv, ctx=ctx)
+    out.update(pairs=pt, matches=matches, match_count=mcount, transforms=tr, inlier_mask=mask, stats=st, warped=warped)
+    return out

@@ -170,3 +170,47 @@ def solve_matches(kp_a, kp_b, matches, count, whichTransform, ransacReprojThresh
                                             int(ransacReprojThresh), float(minConsensusRatio), tr.data_ptr(),
                                             mask.data_ptr(), st.data_ptr(), torch.cuda.current_stream(dv).cuda_stream))
     return tr, mask[:cap], st
+
+
+def pairSeed(seed, p):
+    """The seed micv_ransac_solve_pairs_dev gives pair p: splitmix64(seed + p), the sum wrapping in 64 bits -- what
+    solve_matches takes to reproduce element p of solve_pairs."""
+    m = (1 << 64) - 1
+    z = ((int(seed) + int(p)) + 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
+
+
+def solve_pairs(kp, pairs, matches, match_count, whichTransform, ransacReprojThresh=3, maxIters=2000, minConsensusRatio=0.75,
+                seed=0, ctx=None):
+    """solve_matches on a batch of pairs, four launches whatever their number (micv_ransac_solve_pairs_dev).  kp [images,
+    kcap, 4] float32 CUDA keypoints, pairs as for match.matchPairs, matches [npairs, mcap, 2] and match_count [npairs] as
+    matchPairs left them.  -> (transforms [npairs, 2, 2, 3], inlier mask [npairs, mcap], stats [npairs, 3]); element p holds
+    the bytes of solve_matches(kp[a], kp[b], matches[p], match_count[p:p+1], ..., seed=pairSeed(seed, p)).  Nothing is read
+    back."""
+    import torch
+    from .match import pairList
+    k = _type(whichTransform)
+    if not (isinstance(kp, torch.Tensor) and kp.is_cuda and kp.dim() == 3 and kp.shape[2] == 4 and kp.dtype == torch.float32
+            and kp.stride(2) == 1 and (kp.shape[1] <= 1 or kp.stride(1) == 4)):
+        raise ValueError("kp: need an [images, kcap, 4] float32 CUDA tensor with dense rows")
+    images, kcap = int(kp.shape[0]), int(kp.shape[1])
+    dv = kp.device
+    pt = pairList(pairs, images, dv)
+    npairs = int(pt.shape[0])
+    if not (matches.is_cuda and matches.dtype == torch.int32 and matches.is_contiguous() and matches.dim() == 3
+            and matches.shape[0] == npairs and matches.shape[2] == 2):
+        raise ValueError("matches: need a contiguous [npairs, mcap, 2] int32 CUDA tensor")
+    if not (match_count.is_cuda and match_count.dtype == torch.int64 and match_count.is_contiguous() and match_count.numel() == npairs):
+        raise ValueError("match_count: need a contiguous [npairs] int64 CUDA tensor")
+    mcap = int(matches.shape[1])
+    tr = torch.empty((npairs, 2, 2, 3), dtype=torch.float32, device=dv)
+    mask = torch.empty((npairs, max(mcap, 1)), dtype=torch.uint8, device=dv)
+    st = torch.empty((npairs, 3), dtype=torch.int32, device=dv)
+    check(lib.micv_ransac_solve_pairs_dev(_ctx_for(kp, ctx).handle, kp.data_ptr(), images, (kp.stride(0) if images > 1 else kcap * 4) * 4,
+                                          kcap, pt.data_ptr(), npairs, matches.data_ptr(), match_count.data_ptr(), mcap,
+                                          int(seed) & ((1 << 64) - 1), int(maxIters), k, int(ransacReprojThresh),
+                                          float(minConsensusRatio), tr.data_ptr(), mask.data_ptr(), st.data_ptr(),
+                                          torch.cuda.current_stream(dv).cuda_stream))
+    return tr, mask[:, :mcap], st
