@@ -1195,6 +1195,36 @@ int micv_pf_model_host(micv_pf *pf, uint8_t *patch, float *hist);
 int micv_pf_track_seq_host(micv_pf *pf, const uint8_t *const *frames, int nframes, size_t stride,
                            micv_pf_state *states, float *particles);
 
+/* A group of filters ticked together: the six trackers of the ps6 driver, or several targets in one video.  A group
+ * BORROWS its members: it owns no particles, model or tables, only a device table of member descriptors (uploaded at
+ * create, synchronous like micv_pf_create) and, for the host-sequence calls, two frame buffers.  Members share the
+ * device and the frame's rows, cols and channels and may differ in everything else.  MICV_EINVAL for count outside
+ * 1 .. MICV_PF_GROUP_MAX, a null member, the same member twice, members on different devices or of different frame
+ * sizes.  The members live on after micv_pf_group_destroy; destroying a member before its group, or using a member
+ * (through its group or alone) from two streams at once, is the caller's error.
+ * micv_pf_group_tick_dev: frames / strides are HOST arrays of device pointers and row strides, nframes == 1 (one frame
+ * for every member) or nframes == count (frame k for member k); they travel by value in the launch arguments, so the
+ * call copies nothing, allocates nothing and never synchronises.  Three launches on `stream` whatever count is: score
+ * (grid max n x count; a workgroup past its member's n exits at once), resample + estimate and model update (one
+ * workgroup per member each).  Afterwards EVERY member is, byte for byte, in the state micv_pf_tick_dev on its own
+ * frame would have left it in (particles, weights, model, histogram, state, status bits): the stages are the same code.
+ * states_dev (device, may be NULL): count entries, entry k member k's.  Every accessor above and micv_ps6_overlay_dev
+ * work on the members afterwards; group ticks and single ticks of members may be interleaved on one stream in any
+ * order (the group caches nothing).  MICV_EINVAL (nothing enqueued) for nframes other than 1 or count, a null frame
+ * or a stride < img_cols * channels.
+ * micv_pf_group_track_seq_host: micv_pf_track_seq_host for the whole group over ONE host video: each frame uploaded
+ * once, the upload of frame t + 1 beside tick t, two streams of its own, blocking.  states: [nframes][count];
+ * particles: NULL, or count pointers, each NULL or [nframes][n_k][2] f32.  Byte-identical to micv_pf_track_seq_host on
+ * each member alone. */
+#define MICV_PF_GROUP_MAX 64
+typedef struct micv_pf_group micv_pf_group;
+int micv_pf_group_create(micv_pf *const *members, int count, micv_pf_group **group);
+void micv_pf_group_destroy(micv_pf_group *group);
+int micv_pf_group_tick_dev(micv_pf_group *g, const uint8_t *const *frames, const size_t *strides, int nframes,
+                           micv_stream stream, micv_pf_state *states_dev);
+int micv_pf_group_track_seq_host(micv_pf_group *g, const uint8_t *const *frames, int nframes, size_t stride,
+                                 micv_pf_state *states, float *const *particles);
+
 /* ----------------------------------- ps7: motion history ----- */
 
 /* mhi::frameDifference, ps7_cpp/lib/MotionHistory.cpp:26-77, for single-channel CV_8U frames:
@@ -1708,6 +1738,19 @@ int micv_ps6_tick_display_host(micv_pf *pf, const uint8_t *frame, size_t stride,
 int micv_ps6_track_display_seq_host(micv_pf *pf, const uint8_t *const *frames, int nframes, size_t stride, const double *dot_color,
                                     float bbox_w, float bbox_h, const double *box_color, const int *save, int nsave, int all_frames,
                                     uint8_t *const *out_frames, size_t ostride, micv_pf_state *states);
+/* The same for a group over one host video (micv_pf_group_track_seq_host with the driver's pictures): every member gets
+ * its OWN annotated pictures, as the reference's six pfDriver runs each paint their own copy of the video.  For every
+ * frame t that member k keeps (t in save[k][0 .. nsave[k]), or every frame with all_frames != 0) the device frame buffer
+ * is copied into a scratch picture, painted there by the overlay launch above from member k's particles and state
+ * (bbox_wh[k] = {width, height} of its box) and downloaded into out_frames[k][j]; the frame buffer itself is never
+ * painted, and the next upload into it waits for these copies as for the tick.  save, nsave and out_frames: count
+ * entries; save[k] / out_frames[k] may be NULL where member k keeps nothing.  out_frames[k][j] and states[t][k]
+ * ([nframes][count]) are byte-identical to micv_ps6_track_display_seq_host on member k alone with the same save list;
+ * the argument rules of that call hold per member.  Blocking. */
+int micv_ps6_group_track_display_seq_host(micv_pf_group *g, const uint8_t *const *frames, int nframes, size_t stride,
+                                          const double *dot_color, const float *bbox_wh, const double *box_color,
+                                          const int *const *save, const int *nsave, int all_frames,
+                                          uint8_t *const *const *out_frames, size_t ostride, micv_pf_state *states);
 
 /* ------------------------------------------------------------------ ps0 ------ */
 /* ps0 of the reference (ProblemSets/ps0_cpp/main.cpp) on the device.  OpenCV's behaviour is restated, PARITY UNPINNED

@@ -277,7 +277,12 @@ SIGNATURES = {
     "micv_pf_weights_host": (i32, [vp, vp]),
     "micv_pf_model_host": (i32, [vp, vp, vp]),
     "micv_pf_track_seq_host": (i32, [vp, vp, i32, sz, vp, vp]),
+    "micv_pf_group_create": (i32, [vp, i32, C.POINTER(vp)]),
+    "micv_pf_group_destroy": (None, [vp]),
+    "micv_pf_group_tick_dev": (i32, [vp, vp, vp, i32, vp, vp]),
+    "micv_pf_group_track_seq_host": (i32, [vp, vp, i32, sz, vp, vp]),
     # ps6 driver
+    "micv_ps6_group_track_display_seq_host": (i32, [vp, vp, i32, sz, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
     "micv_draw_particles_dev": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, vp, vp]),
     "micv_draw_particles_host": (i32, [vp, vp, i32, i32, i32, sz, vp, i32, vp]),
     "micv_draw_rectangle_dev": (i32, [vp, vp, i32, i32, i32, sz, i32, i32, i32, i32, vp, vp]),

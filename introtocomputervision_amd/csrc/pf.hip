@@ -11,7 +11,11 @@
 //                       float mean / variance on lane 0, the state out.
 //   pf_model_kernel     one workgroup: the blend at the rounded mean; in histogram mode the blend's
 //                       normalized histogram becomes the model histogram.
+// A group (micv_pf_group) ticks up to 64 filters in the same three launches: each stage is written once, and the single
+// tick's kernels and the group's are two entries into it, so a member's bytes cannot depend on the entry.  A group owns
+// a device table of member descriptors and nothing else; the frames travel in the launch arguments.
 // Arithmetic: mi_cv.h "ps6: particle filter" and DESIGN.md section 2.  -ffp-contract=off: no fma here.
+#include <algorithm>
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -71,89 +75,15 @@ __device__ inline void l2_normalize(const unsigned *h, float *out) {
     for (int b = 0; b < kBins; b++) out[b] = (float)((double)h[b] * inv);
 }
 
-// Displace particle blockIdx.x, test it, score its patch: moved[i], sim[i] (0 outside the frame).
-__global__ void __launch_bounds__(kScoreThreads)
-pf_score_kernel(const uint8_t *__restrict__ frame, size_t stride, int rows, int cols, int ch, int mrows, int mcols,
-                int mode, uint32_t flags, double mse_sigma, const float2 *__restrict__ parts,
-                const double2 *__restrict__ disp, const uint8_t *__restrict__ model, const float *__restrict__ mhist,
-                float2 *__restrict__ moved, double *__restrict__ sim) {
-    __shared__ unsigned bins[kScoreThreads / 64][3 * kBins];
-    __shared__ unsigned long long red[kScoreThreads / 64];
-    const int i = blockIdx.x;
-    const float2 p0 = parts[i];
-    const double2 g = disp[i];
-    const float px = (float)((double)p0.x + g.x), py = (float)((double)p0.y + g.y);
-    if (threadIdx.x == 0) moved[i] = make_float2(px, py);
-    if (!(px >= 0.f && px < (float)cols && py >= 0.f && py < (float)rows)) {  // (finite tables: never NaN)
-        if (threadIdx.x == 0) sim[i] = 0.0;
-        return;
-    }
-    PatchGeom pg{frame, stride, rows, cols, ch, mrows, mcols, cv_round(px) - (mcols + 1) / 2,
-                 cv_round(py) - (mrows + 1) / 2};
-    const bool inside = pg.x0 >= 0 && pg.x0 + mcols <= cols;
-    const int rb = mcols * ch, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (mode == MICV_PF_MSE) {
-        const bool sgn = flags & MICV_PF_MSE_SIGNED;
-        unsigned long long acc = 0;
-        for (int r = wave; r < mrows; r += kScoreThreads / 64) {
-            const uint8_t *row = frame + (size_t)clampi(pg.y0 + r, 0, rows - 1) * stride;
-            const uint8_t *mrow = model + (size_t)r * rb;
-            for (int b = lane; b < rb; b += 64) {
-                const int m = mrow[b], c = (int)patch_byte(pg, row, b, inside);
-                const int d = m - c;
-                acc += (unsigned)(sgn ? d * d : (d > 0 ? min(d * d, 255) : 0));
-            }
-        }
-        wave_sum_u64(acc, red);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long s = 0;
-            for (int w = 0; w < kScoreThreads / 64; w++) s += red[w];
-            const double mse = (double)s / (double)(mrows * mcols);
-            sim[i] = pf_exp(-mse / (2 * mse_sigma * mse_sigma));
-        }
-        return;
-    }
-    // MICV_PF_HIST
-    for (int k = threadIdx.x; k < (kScoreThreads / 64) * 3 * kBins; k += kScoreThreads) (&bins[0][0])[k] = 0;
-    __syncthreads();
-    for (int r = wave; r < mrows; r += kScoreThreads / 64) {
-        const uint8_t *row = frame + (size_t)clampi(pg.y0 + r, 0, rows - 1) * stride;
-        for (int b = lane; b < rb; b += 64) {
-            const int c = ch == 1 ? 0 : b % 3;
-            atomicAdd(&bins[wave][c * kBins + (patch_byte(pg, row, b, inside) >> 3)], 1u);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < ch * kBins) {
-        unsigned s = 0;
-        for (int w = 0; w < kScoreThreads / 64; w++) s += bins[w][threadIdx.x];
-        bins[0][threadIdx.x] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double comp = 0;
-        for (int c = 0; c < ch; c++) {
-            float h[kBins];
-            l2_normalize(&bins[0][c * kBins], h);
-            double chi = 0;
-            for (int b = 0; b < kBins; b++) {
-                const float a = mhist[c * kBins + b];
-                const float d = a - h[b];
-                if (fabs((double)a) > DBL_EPSILON) chi += (double)d * (double)d / (double)a;
-            }
-            comp += chi;
-        }
-        comp /= (double)ch;
-        sim[i] = pf_exp(-comp);
-    }
-}
+// The stages of a tick, each written once; the single tick's kernels and the group's (below) are two entries into each.
+// Resampling is a function.  Scoring and the model update are text (pf_score_body.hpp, pf_model_body.hpp): as inline
+// functions they changed the single tick's register allocation (profiles/pf_group/resources.txt), as text they do not.
 
 // Weights, resampling and the estimate: one workgroup of kTailThreads.
-__global__ void __launch_bounds__(kTailThreads)
-pf_resample_kernel(int n, const double *__restrict__ sim, const float *__restrict__ uni,
-                   const float2 *__restrict__ moved, float *__restrict__ weights, float2 *__restrict__ parts,
-                   micv_pf_state *__restrict__ state, micv_pf_state *__restrict__ state_out) {
+__device__ __forceinline__ void
+pf_resample_body(int n, const double *__restrict__ sim, const float *__restrict__ uni,
+                 const float2 *__restrict__ moved, float *__restrict__ weights, float2 *__restrict__ parts,
+                 micv_pf_state *__restrict__ state, micv_pf_state *__restrict__ state_out) {
     __shared__ double s_sim[kMaxN];
     __shared__ float s_cum[kMaxN];
     // the resampled particles, written only after the last read of s_sim (48 KiB in all): lane 0's sequential
@@ -229,43 +159,77 @@ pf_resample_kernel(int n, const double *__restrict__ sim, const float *__restric
     }
 }
 
-// updateModel at the rounded estimate: one workgroup of kTailThreads.
+// The single tick: particle blockIdx.x / one workgroup / one workgroup.
+__global__ void __launch_bounds__(kScoreThreads)
+pf_score_kernel(const uint8_t *__restrict__ frame, size_t stride, int rows, int cols, int ch, int mrows, int mcols,
+                int mode, uint32_t flags, double mse_sigma, const float2 *__restrict__ parts,
+                const double2 *__restrict__ disp, const uint8_t *__restrict__ model, const float *__restrict__ mhist,
+                float2 *__restrict__ moved, double *__restrict__ sim) {
+    const int i = blockIdx.x;
+#include "pf_score_body.hpp"
+}
+
+__global__ void __launch_bounds__(kTailThreads)
+pf_resample_kernel(int n, const double *__restrict__ sim, const float *__restrict__ uni,
+                   const float2 *__restrict__ moved, float *__restrict__ weights, float2 *__restrict__ parts,
+                   micv_pf_state *__restrict__ state, micv_pf_state *__restrict__ state_out) {
+    pf_resample_body(n, sim, uni, moved, weights, parts, state, state_out);
+}
+
 __global__ void __launch_bounds__(kTailThreads)
 pf_model_kernel(const uint8_t *__restrict__ frame, size_t stride, int rows, int cols, int ch, int mrows, int mcols,
                 int mode, float fa, float fb, const micv_pf_state *__restrict__ state,
                 const uint8_t *__restrict__ model0, uint8_t *__restrict__ model, float *__restrict__ mhist) {
-    __shared__ unsigned bins[kTailThreads / 64][3 * kBins];
-    const float lim = 16777216.f;
-    const float ex = fminf(fmaxf(state->x, -lim), lim), ey = fminf(fmaxf(state->y, -lim), lim);
-    PatchGeom pg{frame, stride, rows, cols, ch, mrows, mcols, cv_round(ex) - (mcols + 1) / 2,
-                 cv_round(ey) - (mrows + 1) / 2};
-    const bool inside = pg.x0 >= 0 && pg.x0 + mcols <= cols;
-    const bool hist = mode == MICV_PF_HIST;
-    const uint8_t *old = hist ? model0 : model;
-    const int rb = mcols * ch, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (hist) {
-        for (int k = threadIdx.x; k < (kTailThreads / 64) * 3 * kBins; k += kTailThreads) (&bins[0][0])[k] = 0;
-        __syncthreads();
-    }
-    for (int r = wave; r < mrows; r += kTailThreads / 64) {
-        const uint8_t *row = frame + (size_t)clampi(pg.y0 + r, 0, rows - 1) * stride;
-        for (int b = lane; b < rb; b += 64) {
-            const size_t k = (size_t)r * rb + b;
-            const float t = (float)patch_byte(pg, row, b, inside) * fa + (float)old[k] * fb;
-            const int v = clampi((int)rintf(t), 0, 255);  // saturate_cast<uchar>(float): cvRound, then clamp
-            model[k] = (uint8_t)v;
-            if (hist) atomicAdd(&bins[wave][(ch == 1 ? 0 : b % 3) * kBins + (v >> 3)], 1u);
-        }
-    }
-    if (!hist) return;
-    __syncthreads();
-    if (threadIdx.x < ch * kBins) {
-        unsigned s = 0;
-        for (int w = 0; w < kTailThreads / 64; w++) s += bins[w][threadIdx.x];
-        bins[0][threadIdx.x] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < ch) l2_normalize(&bins[0][threadIdx.x * kBins], mhist + threadIdx.x * kBins);
+#include "pf_model_body.hpp"
+}
+
+// The group's tick: member blockIdx.y of the descriptor table `members`, its frame out of the launch arguments (64 x 16
+// bytes at the cap).  Everything a workgroup takes from the table and from `f` is uniform over the workgroup.
+struct GroupFrames {
+    const uint8_t *frame[MICV_PF_GROUP_MAX];
+    size_t stride[MICV_PF_GROUP_MAX];
+};
+
+// Grid (max n, count): a workgroup past its member's n returns having read the descriptor alone.
+__global__ void __launch_bounds__(kScoreThreads)
+pf_group_score_kernel(const PfMember *__restrict__ members, const GroupFrames f) {
+    const PfMember &m = members[blockIdx.y];
+    const int i = blockIdx.x;
+    if (i >= m.n) return;
+    const uint8_t *__restrict__ frame = f.frame[blockIdx.y];
+    const size_t stride = f.stride[blockIdx.y];
+    const int rows = m.rows, cols = m.cols, ch = m.ch, mrows = m.mrows, mcols = m.mcols, mode = m.mode;
+    const uint32_t flags = m.flags;
+    const double mse_sigma = m.mse_sigma;
+    const float2 *__restrict__ parts = m.parts;
+    const double2 *__restrict__ disp = m.disp;
+    const uint8_t *__restrict__ model = m.model;
+    const float *__restrict__ mhist = m.hist;
+    float2 *__restrict__ moved = m.moved;
+    double *__restrict__ sim = m.sim;
+#include "pf_score_body.hpp"
+}
+
+// Grid (count): one workgroup per member.  states_out: count entries or NULL.
+__global__ void __launch_bounds__(kTailThreads)
+pf_group_resample_kernel(const PfMember *__restrict__ members, micv_pf_state *__restrict__ states_out) {
+    const int k = blockIdx.x;
+    const PfMember &m = members[k];
+    pf_resample_body(m.n, m.sim, m.uni, m.moved, m.weights, m.parts, m.state, states_out ? states_out + k : nullptr);
+}
+
+__global__ void __launch_bounds__(kTailThreads)
+pf_group_model_kernel(const PfMember *__restrict__ members, const GroupFrames f) {
+    const PfMember &m = members[blockIdx.x];
+    const uint8_t *__restrict__ frame = f.frame[blockIdx.x];
+    const size_t stride = f.stride[blockIdx.x];
+    const int rows = m.rows, cols = m.cols, ch = m.ch, mrows = m.mrows, mcols = m.mcols, mode = m.mode;
+    const float fa = m.fa, fb = m.fb;
+    const micv_pf_state *__restrict__ state = m.state;
+    const uint8_t *__restrict__ model0 = m.model0;
+    uint8_t *__restrict__ model = m.model;
+    float *__restrict__ mhist = m.hist;
+#include "pf_model_body.hpp"
 }
 
 // -------------------------------------------------------------------------------------------- host
@@ -335,6 +299,41 @@ int frame_buffers(micv_pf *pf) {
     return MICV_OK;
 }
 
+// A member's row as of NOW: the buffer pointers and the scalars are copied, and a group uploads its rows once, at create.
+// That holds because no micv_pf call reallocates a buffer or changes n, mode, flags, sigma or alpha after micv_pf_create;
+// a setter or a reallocation added to micv_pf later must refresh (or invalidate) the tables of the groups that hold it.
+PfMember describe(const micv_pf *pf) {
+    PfMember m{};
+    m.rows = pf->rows, m.cols = pf->cols, m.ch = pf->ch, m.mrows = pf->mrows, m.mcols = pf->mcols, m.n = pf->n;
+    m.mode = pf->mode, m.flags = pf->flags, m.mse_sigma = pf->mse_sigma, m.fa = pf->fa, m.fb = pf->fb;
+    m.parts = pf->parts, m.moved = pf->moved, m.disp = pf->disp, m.uni = pf->uni, m.sim = pf->sim;
+    m.weights = pf->weights, m.model = pf->model, m.model0 = pf->model0, m.hist = pf->hist, m.state = pf->state;
+    return m;
+}
+
+// Three launches whatever count is; the frames go by value (a shared frame is repeated for every member).
+int enqueue_group_tick(micv_pf_group *g, const uint8_t *const *frames, const size_t *strides, int nframes, hipStream_t s,
+                       micv_pf_state *states_out) {
+    GroupFrames f{};
+    for (int k = 0; k < g->count; k++) {
+        f.frame[k] = frames[nframes == 1 ? 0 : k];
+        f.stride[k] = strides[nframes == 1 ? 0 : k];
+    }
+    pf_group_score_kernel<<<dim3(g->max_n, g->count), kScoreThreads, 0, s>>>(g->table, f);
+    MICV_LAUNCH_CHECK();
+    pf_group_resample_kernel<<<g->count, kTailThreads, 0, s>>>(g->table, states_out);
+    MICV_LAUNCH_CHECK();
+    pf_group_model_kernel<<<g->count, kTailThreads, 0, s>>>(g->table, f);
+    MICV_LAUNCH_CHECK();
+    return MICV_OK;
+}
+
+int group_frame_buffers(micv_pf_group *g) {
+    for (auto &b : g->frame_buf)
+        if (!b) MICV_HIP(hipMalloc(&b, g->frame_bytes()));
+    return MICV_OK;
+}
+
 }  // namespace
 
 // For ps6.hip (pf.hpp).
@@ -342,6 +341,11 @@ int pf_enqueue_tick(micv_pf *pf, const uint8_t *frame, size_t stride, hipStream_
     return enqueue_tick(pf, frame, stride, s, state_out);
 }
 int pf_frame_buffers(micv_pf *pf) { return frame_buffers(pf); }
+int pf_group_enqueue_tick(micv_pf_group *g, const uint8_t *const *frames, const size_t *strides, int nframes, hipStream_t s,
+                          micv_pf_state *states_out) {
+    return enqueue_group_tick(g, frames, strides, nframes, s, states_out);
+}
+int pf_group_frame_buffers(micv_pf_group *g) { return group_frame_buffers(g); }
 
 }  // namespace micv
 
@@ -550,6 +554,124 @@ int micv_pf_track_seq_host(micv_pf *pf, const uint8_t *const *frames, int nframe
     MICV_HIP(hipMemcpyAsync(states, sc.st, (size_t)nframes * sizeof(micv_pf_state), hipMemcpyDeviceToHost, sc.run));
     if (particles)
         MICV_HIP(hipMemcpyAsync(particles, sc.pt, (size_t)nframes * pbytes, hipMemcpyDeviceToHost, sc.run));
+    MICV_HIP(hipStreamSynchronize(sc.run));
+    return MICV_OK;
+}
+
+int micv_pf_group_create(micv_pf *const *members, int count, micv_pf_group **out) {
+    MICV_REQUIRE(members && out, "micv_pf_group_create: null argument");
+    *out = nullptr;
+    MICV_REQUIRE(count >= 1 && count <= MICV_PF_GROUP_MAX, "micv_pf_group_create: count = %d outside 1 .. %d", count,
+                 MICV_PF_GROUP_MAX);
+    for (int k = 0; k < count; k++) {
+        MICV_REQUIRE(members[k], "micv_pf_group_create: member %d is null", k);
+        for (int j = 0; j < k; j++) MICV_REQUIRE(members[j] != members[k], "micv_pf_group_create: member %d is member %d", k, j);
+        const micv_pf *a = members[0], *b = members[k];
+        MICV_REQUIRE(b->device == a->device, "micv_pf_group_create: member %d lives on device %d, member 0 on %d", k, b->device,
+                     a->device);
+        MICV_REQUIRE(b->rows == a->rows && b->cols == a->cols && b->ch == a->ch,
+                     "micv_pf_group_create: member %d was made for %d x %d x %d frames, member 0 for %d x %d x %d", k, b->rows,
+                     b->cols, b->ch, a->rows, a->cols, a->ch);
+    }
+    std::unique_ptr<micv_pf_group> g(new micv_pf_group);
+    g->device = members[0]->device, g->count = count;
+    g->rows = members[0]->rows, g->cols = members[0]->cols, g->ch = members[0]->ch;
+    g->members.assign(members, members + count);
+    std::vector<PfMember> table(count);
+    for (int k = 0; k < count; k++) {
+        table[k] = describe(members[k]);
+        g->max_n = std::max(g->max_n, members[k]->n);
+    }
+    MICV_HIP(hipSetDevice(g->device));
+    MICV_HIP(hipMalloc(&g->table, count * sizeof(PfMember)));
+    MICV_HIP(hipMemcpy(g->table, table.data(), count * sizeof(PfMember), hipMemcpyHostToDevice));
+    *out = g.release();
+    return MICV_OK;
+}
+
+void micv_pf_group_destroy(micv_pf_group *g) {
+    if (!g) return;
+    (void)hipSetDevice(g->device);
+    (void)hipDeviceSynchronize();  // nothing enqueued on its table or buffers may still run
+    delete g;
+}
+
+int micv_pf_group_tick_dev(micv_pf_group *g, const uint8_t *const *frames, const size_t *strides, int nframes,
+                           micv_stream stream, micv_pf_state *states_dev) {
+    MICV_REQUIRE(g && frames && strides, "micv_pf_group_tick_dev: null argument");
+    MICV_REQUIRE(nframes == 1 || nframes == g->count, "micv_pf_group_tick_dev: %d frames for %d members, need 1 or %d", nframes,
+                 g->count, g->count);
+    for (int k = 0; k < nframes; k++) {
+        MICV_REQUIRE(frames[k], "micv_pf_group_tick_dev: frame %d is null", k);
+        MICV_REQUIRE(strides[k] >= (size_t)g->cols * g->ch, "micv_pf_group_tick_dev: stride %zu of frame %d < %d", strides[k], k,
+                     g->cols * g->ch);
+    }
+    MICV_HIP(hipSetDevice(g->device));
+    return enqueue_group_tick(g, frames, strides, nframes, static_cast<hipStream_t>(stream), states_dev);
+}
+
+int micv_pf_group_track_seq_host(micv_pf_group *g, const uint8_t *const *frames, int nframes, size_t stride,
+                                 micv_pf_state *states, float *const *particles) {
+    MICV_REQUIRE(g && frames && states && nframes >= 1, "micv_pf_group_track_seq_host: bad argument");
+    const size_t rb = (size_t)g->cols * g->ch;
+    MICV_REQUIRE(stride >= rb, "micv_pf_group_track_seq_host: stride %zu < %zu", stride, rb);
+    for (int t = 0; t < nframes; t++) MICV_REQUIRE(frames[t], "micv_pf_group_track_seq_host: frame %d is null", t);
+    MICV_HIP(hipSetDevice(g->device));
+    MICV_TRY(group_frame_buffers(g));
+    const int count = g->count;
+    struct Scope {  // released on every way out, after everything enqueued has finished
+        hipStream_t up = nullptr, run = nullptr;
+        std::vector<hipEvent_t> ev;
+        std::vector<void *> mem;
+        ~Scope() {
+            for (hipStream_t s : {up, run})
+                if (s) (void)hipStreamSynchronize(s);
+            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+            for (hipStream_t s : {up, run})
+                if (s) (void)hipStreamDestroy(s);
+            for (void *p : mem)
+                if (p) (void)hipFree(p);
+        }
+    } sc;
+    MICV_HIP(hipStreamCreateWithFlags(&sc.up, hipStreamNonBlocking));
+    MICV_HIP(hipStreamCreateWithFlags(&sc.run, hipStreamNonBlocking));
+    sc.mem.assign(1 + (size_t)count, nullptr);  // the states, then member k's particles of every tick
+    MICV_HIP(hipMalloc(&sc.mem[0], (size_t)nframes * count * sizeof(micv_pf_state)));
+    for (int k = 0; particles && k < count; k++)
+        if (particles[k]) MICV_HIP(hipMalloc(&sc.mem[1 + k], (size_t)nframes * g->members[k]->n * sizeof(float2)));
+    std::vector<hipEvent_t> ev_up(nframes), ev_tick(nframes);
+    sc.ev.reserve(2 * (size_t)nframes);
+    for (auto *v : {&ev_up, &ev_tick})
+        for (auto &e : *v) {
+            MICV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            sc.ev.push_back(e);
+        }
+    micv_pf_state *dst = static_cast<micv_pf_state *>(sc.mem[0]);
+    auto upload = [&](int t) -> int {
+        if (t >= 2) MICV_HIP(hipStreamWaitEvent(sc.up, ev_tick[t - 2], 0));  // its buffer's last reader
+        MICV_HIP(hipMemcpy2DAsync(g->frame_buf[t & 1], rb, frames[t], stride, rb, g->rows, hipMemcpyHostToDevice, sc.up));
+        MICV_HIP(hipEventRecord(ev_up[t], sc.up));
+        return MICV_OK;
+    };
+    MICV_TRY(upload(0));
+    for (int t = 0; t < nframes; t++) {
+        const uint8_t *buf = g->frame_buf[t & 1];
+        MICV_HIP(hipStreamWaitEvent(sc.run, ev_up[t], 0));
+        MICV_TRY(enqueue_group_tick(g, &buf, &rb, 1, sc.run, dst + (size_t)t * count));
+        for (int k = 0; k < count; k++)
+            if (sc.mem[1 + k]) {
+                const size_t pbytes = (size_t)g->members[k]->n * sizeof(float2);
+                MICV_HIP(hipMemcpyAsync(static_cast<char *>(sc.mem[1 + k]) + (size_t)t * pbytes, g->members[k]->parts, pbytes,
+                                        hipMemcpyDeviceToDevice, sc.run));
+            }
+        MICV_HIP(hipEventRecord(ev_tick[t], sc.run));
+        if (t + 1 < nframes) MICV_TRY(upload(t + 1));  // (a pageable copy holds this thread: tick t runs meanwhile)
+    }
+    MICV_HIP(hipMemcpyAsync(states, sc.mem[0], (size_t)nframes * count * sizeof(micv_pf_state), hipMemcpyDeviceToHost, sc.run));
+    for (int k = 0; k < count; k++)
+        if (sc.mem[1 + k])
+            MICV_HIP(hipMemcpyAsync(particles[k], sc.mem[1 + k], (size_t)nframes * g->members[k]->n * sizeof(float2),
+                                    hipMemcpyDeviceToHost, sc.run));
     MICV_HIP(hipStreamSynchronize(sc.run));
     return MICV_OK;
 }

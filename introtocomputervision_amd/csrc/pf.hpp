@@ -1,6 +1,8 @@
 // pf.hpp -- the particle filter's handle (pf.hip) for the files that work on its device state (ps6.hip: the driver's
 // overlay reads the particles and the estimate where the tick left them).
 #pragma once
+#include <vector>
+
 #include "common.hpp"
 
 struct micv_pf {
@@ -30,8 +32,48 @@ struct micv_pf {
 };
 
 namespace micv {
+// What the three stages of a tick read of one filter: a row of a group's device table (pf.hip).  Pointers into the
+// member's own buffers; the group owns none of them.  The row is a snapshot taken at micv_pf_group_create: everything in it
+// is fixed for a micv_pf's lifetime today, and must stay so or be refreshed in every group (pf.hip, describe()).
+struct PfMember {
+    int rows, cols, ch, mrows, mcols, n, mode;
+    uint32_t flags;
+    double mse_sigma;
+    float fa, fb;
+    float2 *parts, *moved;
+    const double2 *disp;
+    const float *uni;
+    double *sim;
+    float *weights;
+    uint8_t *model;
+    const uint8_t *model0;
+    float *hist;
+    micv_pf_state *state;
+};
+}  // namespace micv
+
+struct micv_pf_group {
+    int device = 0, count = 0, max_n = 0;
+    int rows = 0, cols = 0, ch = 0;  // the frame every member was made for
+    std::vector<micv_pf *> members;  // borrowed
+    micv::PfMember *table = nullptr;  // device, count rows
+    uint8_t *frame_buf[2] = {nullptr, nullptr};  // host-frame staging of the sequence calls, allocated on first use
+    ~micv_pf_group() {
+        (void)hipSetDevice(device);
+        for (void *p : {(void *)table, (void *)frame_buf[0], (void *)frame_buf[1]})
+            if (p) (void)hipFree(p);
+    }
+    size_t frame_bytes() const { return (size_t)rows * cols * ch; }
+};
+
+namespace micv {
 // The three launches of one tick on `s` (pf.hip); the state also goes to state_out (device, may be NULL).
 int pf_enqueue_tick(micv_pf *pf, const uint8_t *frame, size_t stride, hipStream_t s, micv_pf_state *state_out);
 // Allocates pf->frame_buf[0..1] (dense rows x cols x ch) on first use.
 int pf_frame_buffers(micv_pf *pf);
+// The three launches of a group's tick on `s`: nframes == 1 (a shared frame) or g->count (one each); the arguments
+// are checked by the caller.  states_out: device, count entries, may be NULL.
+int pf_group_enqueue_tick(micv_pf_group *g, const uint8_t *const *frames, const size_t *strides, int nframes, hipStream_t s,
+                          micv_pf_state *states_out);
+int pf_group_frame_buffers(micv_pf_group *g);
 }  // namespace micv

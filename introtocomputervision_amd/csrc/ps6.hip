@@ -228,4 +228,106 @@ int micv_ps6_track_display_seq_host(micv_pf *pf, const uint8_t *const *frames, i
     return MICV_OK;
 }
 
+int micv_ps6_group_track_display_seq_host(micv_pf_group *g, const uint8_t *const *frames, int nframes, size_t stride,
+                                          const double *dot_color, const float *bbox_wh, const double *box_color,
+                                          const int *const *save, const int *nsave, int all_frames,
+                                          uint8_t *const *const *out_frames, size_t ostride, micv_pf_state *states) {
+    MICV_REQUIRE(g && frames && states && dot_color && bbox_wh && box_color && nframes >= 1 && (all_frames || nsave),
+                 "micv_ps6_group_track_display_seq_host: bad argument");
+    const int count = g->count;
+    const size_t rb = (size_t)g->cols * g->ch;
+    MICV_REQUIRE(image_ok(g->rows, g->cols, g->ch, stride), "micv_ps6_group_track_display_seq_host: stride %zu < %zu", stride, rb);
+    for (int t = 0; t < nframes; t++) MICV_REQUIRE(frames[t], "micv_ps6_group_track_display_seq_host: frame %d is null", t);
+    // the destinations of member k's frame t: dest[k][first[k][t] .. first[k][t + 1])
+    std::vector<std::vector<int>> first(count, std::vector<int>(nframes + 1, 0));
+    std::vector<std::vector<uint8_t *>> dest(count);
+    for (int k = 0; k < count; k++) {
+        MICV_REQUIRE(all_frames || nsave[k] >= 0, "micv_ps6_group_track_display_seq_host: member %d: nsave = %d", k, nsave[k]);
+        const int nout = all_frames ? nframes : nsave[k];
+        MICV_REQUIRE(nout == 0 || (out_frames && out_frames[k] && ostride >= rb && (all_frames || (save && save[k]))),
+                     "micv_ps6_group_track_display_seq_host: member %d keeps frames, but a list is null or the stride %zu < %zu", k,
+                     ostride, rb);
+        dest[k].resize(nout);
+        for (int j = 0; j < nout; j++) {
+            MICV_REQUIRE(out_frames[k][j], "micv_ps6_group_track_display_seq_host: output %d of member %d is null", j, k);
+            const int t = all_frames ? j : save[k][j];
+            MICV_REQUIRE(t >= 0 && t < nframes, "micv_ps6_group_track_display_seq_host: member %d: save index %d outside 0 .. %d", k,
+                         t, nframes - 1);
+            first[k][t + 1]++;
+        }
+        for (int t = 0; t < nframes; t++) first[k][t + 1] += first[k][t];
+        std::vector<int> fill(first[k].begin(), first[k].end() - 1);
+        for (int j = 0; j < nout; j++) dest[k][fill[all_frames ? j : save[k][j]]++] = out_frames[k][j];
+    }
+    MICV_HIP(hipSetDevice(g->device));
+    MICV_TRY(pf_group_frame_buffers(g));
+    struct Scope {  // released on every way out, after everything enqueued has finished
+        hipStream_t copy = nullptr, run = nullptr;
+        std::vector<hipEvent_t> ev;
+        std::vector<void *> mem;
+        ~Scope() {
+            for (hipStream_t s : {copy, run})
+                if (s) (void)hipStreamSynchronize(s);
+            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+            for (hipStream_t s : {copy, run})
+                if (s) (void)hipStreamDestroy(s);
+            for (void *p : mem)
+                if (p) (void)hipFree(p);
+        }
+    } sc;
+    MICV_HIP(hipStreamCreateWithFlags(&sc.copy, hipStreamNonBlocking));
+    MICV_HIP(hipStreamCreateWithFlags(&sc.run, hipStreamNonBlocking));
+    // the states, then two scratch pictures (frame parity) for every member that keeps a frame
+    sc.mem.assign(1 + 2 * (size_t)count, nullptr);
+    MICV_HIP(hipMalloc(&sc.mem[0], (size_t)nframes * count * sizeof(micv_pf_state)));
+    for (int k = 0; k < count; k++)
+        if (!dest[k].empty())
+            for (int b = 0; b < 2; b++) MICV_HIP(hipMalloc(&sc.mem[1 + 2 * k + b], g->frame_bytes()));
+    std::vector<hipEvent_t> ev_up(nframes), ev_tick(nframes);
+    sc.ev.reserve(2 * (size_t)nframes);
+    for (auto *v : {&ev_up, &ev_tick})
+        for (auto &e : *v) {
+            MICV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            sc.ev.push_back(e);
+        }
+    micv_pf_state *dst = static_cast<micv_pf_state *>(sc.mem[0]);
+    // Uploads and downloads share the copy stream; ticks, the copies into the scratch pictures and the overlays share the
+    // run stream.  ev_tick[t] follows the last reader of frame buffer t & 1 (the tick and every copy out of it), and the
+    // upload of frame t + 2 waits for it.  A scratch picture of parity t & 1 is painted again at frame t + 2 at the
+    // earliest; tick t + 2 waits for upload t + 2, which follows the downloads of frame t on the copy stream.
+    auto upload = [&](int t) -> int {
+        if (t >= 2) MICV_HIP(hipStreamWaitEvent(sc.copy, ev_tick[t - 2], 0));
+        MICV_HIP(hipMemcpy2DAsync(g->frame_buf[t & 1], rb, frames[t], stride, rb, g->rows, hipMemcpyHostToDevice, sc.copy));
+        MICV_HIP(hipEventRecord(ev_up[t], sc.copy));
+        return MICV_OK;
+    };
+    MICV_TRY(upload(0));
+    for (int t = 0; t < nframes; t++) {
+        const uint8_t *buf = g->frame_buf[t & 1];
+        MICV_HIP(hipStreamWaitEvent(sc.run, ev_up[t], 0));
+        MICV_TRY(pf_group_enqueue_tick(g, &buf, &rb, 1, sc.run, dst + (size_t)t * count));
+        bool kept = false;
+        for (int k = 0; k < count; k++) kept |= first[k][t + 1] > first[k][t];
+        for (int k = 0; kept && k < count; k++) {
+            if (first[k][t + 1] == first[k][t]) continue;
+            uint8_t *pic = static_cast<uint8_t *>(sc.mem[1 + 2 * k + (t & 1)]);
+            MICV_HIP(hipMemcpyAsync(pic, buf, g->frame_bytes(), hipMemcpyDeviceToDevice, sc.run));
+            MICV_TRY(launch_overlay(pf_overlay(g->members[k], pic, rb, dot_color, bbox_wh[2 * k], bbox_wh[2 * k + 1], box_color), sc.run));
+        }
+        MICV_HIP(hipEventRecord(ev_tick[t], sc.run));
+        if (t + 1 < nframes) MICV_TRY(upload(t + 1));  // beside tick t
+        if (kept) {
+            MICV_HIP(hipStreamWaitEvent(sc.copy, ev_tick[t], 0));
+            for (int k = 0; k < count; k++)
+                for (int j = first[k][t]; j < first[k][t + 1]; j++)
+                    MICV_HIP(hipMemcpy2DAsync(dest[k][j], ostride, sc.mem[1 + 2 * k + (t & 1)], rb, rb, g->rows, hipMemcpyDeviceToHost,
+                                              sc.copy));
+        }
+    }
+    MICV_HIP(hipMemcpyAsync(states, sc.mem[0], (size_t)nframes * count * sizeof(micv_pf_state), hipMemcpyDeviceToHost, sc.run));
+    MICV_HIP(hipStreamSynchronize(sc.run));
+    MICV_HIP(hipStreamSynchronize(sc.copy));
+    return MICV_OK;
+}
+
 }  // extern "C"

@@ -137,6 +137,73 @@ class ParticleFilter:
         self.close()
 
 
+class FilterGroup:
+    """Up to GROUP_MAX `ParticleFilter`s of one device and one frame size ticked together (micv_pf_group): three launches
+    for the whole group, and afterwards every member is byte for byte where its own `tick` would have left it, so the
+    members' accessors (getParticles, weights, model, ps6.overlayFilter) go on working and group ticks may be mixed
+    with single ticks on one stream.  The group borrows the filters and keeps them alive; close the group first."""
+
+    def __init__(self, filters):
+        self.filters = list(filters)
+        handles = (C.c_void_p * max(len(self.filters), 1))(*[f._h for f in self.filters])
+        h = C.c_void_p()
+        check(lib.micv_pf_group_create(handles, len(self.filters), C.byref(h)))
+        self._h = h
+
+    def __len__(self):
+        return len(self.filters)
+
+    def tick(self, frames):
+        """One tick of every member -> [K, 5] int32 device tensor (row k: member k's state words; nothing synchronised).
+        frames: one CUDA tensor for every member, or a list of K tensors, one each."""
+        import torch
+        frames = [frames] if B.is_dev(frames) else list(frames)
+        if len(frames) not in (1, len(self.filters)):
+            raise ValueError(f"tick: {len(frames)} frames for {len(self.filters)} filters, need 1 or {len(self.filters)}")
+        if any(not B.is_dev(f) for f in frames):
+            raise ValueError("tick: CUDA tensors expected (host frames: track)")
+        strides = [self.filters[0]._check_frame(f) for f in frames]
+        if len({(f.device, B.stream_of(f)) for f in frames}) != 1:
+            raise ValueError("tick: every frame needs the same device and current stream")
+        st = torch.empty((len(self.filters), 5), dtype=torch.int32, device=frames[0].device)
+        ptrs = (C.c_void_p * len(frames))(*[f.data_ptr() for f in frames])
+        check(lib.micv_pf_group_tick_dev(self._h, ptrs, (C.c_size_t * len(frames))(*strides), len(frames),
+                                         B.stream_of(frames[0]), st.data_ptr()))
+        return st
+
+    @staticmethod
+    def states_from_device(st):
+        """The [K, 5] device states of tick as a STATE_DTYPE array of K records (synchronises)."""
+        return st.cpu().numpy().view(STATE_DTYPE).reshape(-1)
+
+    def _host_frames(self, frames, what):
+        frames = [np.asarray(f) for f in frames]
+        if not frames:
+            raise ValueError(f"{what}: no frames")
+        strides = {self.filters[0]._check_frame(f) for f in frames}
+        if len(strides) != 1:
+            raise ValueError(f"{what}: every frame needs the same row stride")
+        return frames, (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames]), strides.pop()
+
+    def track(self, frames, with_particles=False):
+        """Ticks of the whole group over one sequence of host frames, every frame uploaded once -> STATE_DTYPE array
+        [nframes, K] (and a list of K arrays [nframes, n_k, 2]: each member's particles after each tick)."""
+        frames, ptrs, stride = self._host_frames(frames, "track")
+        states = np.zeros((len(frames), len(self.filters)), STATE_DTYPE)
+        parts = [np.empty((len(frames), f.n, 2), np.float32) for f in self.filters] if with_particles else None
+        pp = (C.c_void_p * len(self.filters))(*[p.ctypes.data for p in parts]) if with_particles else None
+        check(lib.micv_pf_group_track_seq_host(self._h, ptrs, len(frames), stride, states.ctypes.data, pp))
+        return (states, parts) if with_particles else states
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.micv_pf_group_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
 def track(frames, model, numParticles, simMode, mseSigma, sampleSigma, initModelPos=(-1.0, -1.0), alpha=0.1,
           **kw):
     """A filter made for frames[0]'s size, run over every frame -> STATE_DTYPE array."""

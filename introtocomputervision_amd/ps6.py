@@ -172,6 +172,40 @@ def trackDisplay(pf, frames, bboxSize, saveFrames=(), allFrames=False, dotColor=
     return states, dict(zip(keep, outs))
 
 
+def trackDisplayGroup(group, frames, bboxSizes, saveFrames, allFrames=False, dotColor=DOT_COLOR, boxColor=BOX_COLOR):
+    """trackDisplay for a pf.FilterGroup over ONE sequence of host frames (micv_ps6_group_track_display_seq_host): every
+    frame is uploaded once and ticked for all members in three launches; each member gets its own annotated pictures.
+    bboxSizes: K (width, height) pairs; saveFrames: K collections of 0-based indices.
+    -> (STATE_DTYPE array [nframes, K], [{index: annotated frame}] * K), member k's part equal to trackDisplay on it."""
+    k = len(group)
+    if len(bboxSizes) != k or len(saveFrames) != k:
+        raise ValueError(f"trackDisplayGroup: {k} bounding-box sizes and {k} save sets expected")
+    frames, ptrs, stride = group._host_frames(frames, "trackDisplayGroup")
+    saves = [sorted({int(t) for t in s}) for s in saveFrames]
+    keeps = [list(range(len(frames))) if allFrames else s for s in saves]
+    outs = [[np.empty(frames[0].shape, np.uint8) for _ in keep] for keep in keeps]
+    sv = [(C.c_int * max(len(s), 1))(*s) for s in saves]
+    op = [(C.c_void_p * max(len(o), 1))(*[a.ctypes.data for a in o]) for o in outs]
+    svp = (C.c_void_p * k)(*[C.addressof(a) for a in sv])
+    opp = (C.c_void_p * k)(*[C.addressof(a) for a in op])
+    nsave = (C.c_int * k)(*[len(s) for s in saves])
+    wh = (C.c_float * (2 * k))(*[float(v) for b in bboxSizes for v in (b[0], b[1])])
+    states = np.zeros((len(frames), k), STATE_DTYPE)
+    rows, cols, ch, _ = _frame_view(frames[0])
+    check(lib.micv_ps6_group_track_display_seq_host(group._h, ptrs, len(frames), stride, _colour(dotColor), wh, _colour(boxColor), svp,
+                                                    nsave, 1 if allFrames else 0, opp, cols * ch, states.ctypes.data))
+    return states, [dict(zip(keep, o)) for keep, o in zip(keeps, outs)]
+
+
+def _driverFilter(f0, bbox, bboxSize, conf, simMode, **kw):
+    """The filter pfDriver makes on its first frame (Solution.cpp:40-58)."""
+    x, y, w, h = (cvRound(v) for v in (bbox[0], bbox[1], bboxSize[0], bboxSize[1]))
+    if not (0 <= x and 0 <= y and w > 0 and h > 0 and x + w <= f0.shape[1] and y + h <= f0.shape[0]):
+        raise ValueError("pfDriver: the bounding box does not lie in the frame")
+    return ParticleFilter(f0[y:y + h, x:x + w].copy(), (f0.shape[1], f0.shape[0]), conf["num_particles"], simMode, conf["mse_sigma"],
+                          conf["dynamics_sigma"], (float(bbox[0]), float(bbox[1])), **kw)
+
+
 def pfDriver(frames, bbox, bboxSize, conf, simMode, saveFrames, allFrames=False, **kw):
     """pfDriver (Solution.cpp:16-107) over host frames: the model is frame 0 at cv::Rect(bbox, bboxSize) (each value
     through cvRound; a copy, not the reference's view into frame 0), the filter starts GAUSSIAN at the bbox with `conf`
@@ -179,12 +213,7 @@ def pfDriver(frames, bbox, bboxSize, conf, simMode, saveFrames, allFrames=False,
     leaves it).  -> (STATE_DTYPE array, {index: annotated frame}); save indices past the sequence are never reached, as
     in the reference."""
     frames = [np.asarray(f) for f in frames]
-    f0 = frames[0]
-    x, y, w, h = (cvRound(v) for v in (bbox[0], bbox[1], bboxSize[0], bboxSize[1]))
-    if not (0 <= x and 0 <= y and w > 0 and h > 0 and x + w <= f0.shape[1] and y + h <= f0.shape[0]):
-        raise ValueError("pfDriver: the bounding box does not lie in the frame")
-    filt = ParticleFilter(f0[y:y + h, x:x + w].copy(), (f0.shape[1], f0.shape[0]), conf["num_particles"], simMode, conf["mse_sigma"],
-                          conf["dynamics_sigma"], (float(bbox[0]), float(bbox[1])), **kw)
+    filt = _driverFilter(frames[0], bbox, bboxSize, conf, simMode, **kw)
     try:
         return trackDisplay(filt, frames, bboxSize, [t for t in saveFrames if 0 <= int(t) < len(frames)], allFrames)
     finally:
@@ -218,3 +247,42 @@ def runProblem3(frames_clean, frames_noisy, cfg, bboxes):
     a = _bbox(bboxes, "pres_debate")
     return {"ps6-3-a": pfDriver(frames_clean, a[0], a[1], config.pf_params(cfg, "pfconf3_head"), MEAN_SHIFT_LT, SAVE_3A),
             "ps6-3-b": pfDriver(frames_clean, HAND_BBOX, HAND_SIZE, config.pf_params(cfg, "pfconf3_hand"), MEAN_SHIFT_LT, SAVE_3B)}
+
+
+def pfDriverGroup(frames, runs):
+    """Several pfDriver runs over ONE sequence of host frames as one group: runs is a list of (bbox, bboxSize, conf, simMode,
+    saveFrames).  -> [(STATE_DTYPE array, {index: annotated frame})] in the order of runs, each equal to pfDriver's."""
+    from .pf import FilterGroup
+    frames = [np.asarray(f) for f in frames]
+    filters, group = [], None
+    try:
+        for bbox, size, conf, mode, _ in runs:
+            filters.append(_driverFilter(frames[0], bbox, size, conf, mode))
+        group = FilterGroup(filters)
+        states, kept = trackDisplayGroup(group, frames, [r[1] for r in runs],
+                                         [[t for t in r[4] if 0 <= int(t) < len(frames)] for r in runs])
+        return [(np.ascontiguousarray(states[:, k]), kept[k]) for k in range(len(runs))]
+    finally:
+        if group is not None:
+            group.close()
+        for f in filters:
+            f.close()
+
+
+def runProblems(frames_clean, frames_noisy, cfg, bboxes):
+    """runProblem1, 2 and 3 together: the six drivers as TWO groups, four filters on the clean frames and two on the noisy
+    ones, so each video is uploaded once and each of its frames ticked for all its filters in three launches.  -> the union
+    of the three dictionaries ("ps6-1-a" .. "ps6-3-b"), byte-equal to them.  The hand's box is bboxes["hand"] where given
+    (((x, y), (w, h)) like the others), the reference's constants otherwise."""
+    from . import config
+    a, e = _bbox(bboxes, "pres_debate"), _bbox(bboxes, "noisy_debate")
+    hand = _bbox(bboxes, "hand") if "hand" in bboxes else (HAND_BBOX, HAND_SIZE)
+    conf = lambda name: config.pf_params(cfg, name)
+    clean = pfDriverGroup(frames_clean, [(a[0], a[1], conf("pfconf1"), MEAN_SQ_ERR, SAVE_1A),
+                                         (hand[0], hand[1], conf("pfconf2"), MEAN_SQ_ERR, SAVE_2A),
+                                         (a[0], a[1], conf("pfconf3_head"), MEAN_SHIFT_LT, SAVE_3A),
+                                         (hand[0], hand[1], conf("pfconf3_hand"), MEAN_SHIFT_LT, SAVE_3B)])
+    noisy = pfDriverGroup(frames_noisy, [(e[0], e[1], conf("pfconf1_noisy"), MEAN_SQ_ERR, SAVE_1E),
+                                         (hand[0], hand[1], conf("pfconf2_noisy"), MEAN_SQ_ERR, SAVE_2B)])
+    return {"ps6-1-a": clean[0], "ps6-1-e": noisy[0], "ps6-2-a": clean[1], "ps6-2-b": noisy[1], "ps6-3-a": clean[2],
+            "ps6-3-b": clean[3]}

@@ -4,12 +4,16 @@
 //                    those two host loops it is the statement of the contract (parity with OpenCV's rasteriser unpinned);
 //   pfDriverDevice   the same files from ONE library call (micv_ps6_track_display_seq_host): one upload per frame, no
 //                    host synchronisation between ticks, a download of only the frames that are kept.
+//   pfDriverGroupDevice  several such runs over one frame list from ONE library call on a filter group
+//                    (micv_ps6_group_track_display_seq_host): the video uploaded once, every frame ticked for all runs in
+//                    three launches, the same files as one pfDriverDevice call per run.
 // Frames come from a std::vector<Mat> instead of cv::VideoCapture; pictures are written through micv_viz::imwrite
 // (PGM / PPM instead of PNG).  Frames handed to the reference's video writer are appended to `video` when it is given.
 #pragma once
 
 #include <climits>
 #include <cmath>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <tuple>
@@ -143,6 +147,95 @@ inline std::vector<micv_pf_state> pfDriverDevice(const Tracking &tracking, const
         const int t = video ? k : save[k];
         if (video) video->push_back(kept[k]);
         if (saveFrames.count(t)) micv_viz::imwrite(framePath(outputPrefix, t, kept[k], ext), kept[k]);
+    }
+    return states;
+}
+
+// `count` pfDriverDevice runs over ONE frame list as one group (micv_ps6_group_track_display_seq_host): the frames of
+// trackings[0] are the video (every other tracking must carry the same frames: count, size, type and bytes are checked, so
+// runs over two videos are two calls), every tracking brings its own bounding box, and run k writes under prefixes[k] the files
+// that pfDriverDevice(trackings[k], confs[k], modes[k], prefixes[k], saveSets[k]) writes.  -> the states of each run.
+inline std::vector<std::vector<micv_pf_state>> pfDriverGroupDevice(const std::vector<Tracking> &trackings,
+                                                                   const std::vector<micv_config::PFConf> &confs,
+                                                                   const std::vector<ParticleFilter::SimilarityMode> &modes,
+                                                                   const std::vector<std::string> &prefixes,
+                                                                   const std::vector<std::unordered_set<int>> &saveSets,
+                                                                   const std::string &ext = "") {
+    const size_t count = trackings.size();
+    micv_shim::require(count >= 1 && confs.size() == count && modes.size() == count && prefixes.size() == count && saveSets.size() == count,
+                       "pfDriverGroup: one configuration, mode, prefix and save set per tracking expected");
+    const std::vector<Mat> &video = trackings[0].frames;
+    micv_shim::require(!video.empty(), "pfDriver: no frames");
+    const Mat &f0 = video[0];
+    const int nframes = static_cast<int>(video.size());
+    std::vector<const uint8_t *> fp;
+    for (const Mat &f : video) {
+        micv_shim::require(f.rows == f0.rows && f.cols == f0.cols && f.type() == f0.type() && f.step == f0.step,
+                           "pfDriver: frames of one size, type and row pitch expected");
+        fp.push_back(f.data);
+    }
+    // one video: a tracking that brings other frames (another video, another length or size) is a mistake, not a request
+    for (size_t k = 1; k < count; k++) {
+        const std::vector<Mat> &other = trackings[k].frames;
+        micv_shim::require(other.size() == video.size(), "pfDriverGroup: every tracking must carry the frames of trackings[0]");
+        for (size_t t = 0; t < other.size(); t++) {
+            const Mat &a = other[t], &b = video[t];
+            bool same = a.rows == b.rows && a.cols == b.cols && a.type() == b.type();
+            for (int r = 0; same && a.data != b.data && r < b.rows; r++)
+                same = std::memcmp(a.data + (size_t)r * a.step, b.data + (size_t)r * b.step, (size_t)b.cols * b.elemSize()) == 0;
+            micv_shim::require(same, "pfDriverGroup: every tracking must carry the frames of trackings[0] (one group per video)");
+        }
+    }
+    std::vector<std::shared_ptr<micv_pf>> filters;
+    std::vector<micv_pf *> members;
+    std::vector<float> bboxWH;
+    for (size_t k = 0; k < count; k++) {
+        const Tracking &tr = trackings[k];
+        const micv_viz::Rect r = toRect(tr.bbox, tr.bboxSize);
+        micv_shim::require(f0.depth() == micv_shim::U8 && r.x >= 0 && r.y >= 0 && r.width > 0 && r.height > 0 && r.x + r.width <= f0.cols &&
+                               r.y + r.height <= f0.rows,
+                           "pfDriver: 8-bit frames expected, and a bounding box inside them");
+        micv_pf *raw = nullptr;
+        micv_shim::check(micv_pf_create(micv_shim::context(), f0.ptr<unsigned char>(r.y) + (size_t)r.x * f0.channels(), r.height, r.width,
+                                        f0.step, f0.channels(), f0.rows, f0.cols, static_cast<int>(confs[k].num_particles),
+                                        static_cast<int>(modes[k]), confs[k].mse_sigma, confs[k].dynamics_sigma, tr.bbox.x, tr.bbox.y, 0.1,
+                                        0, MICV_PF_DEFAULT_SEED, &raw));
+        filters.emplace_back(raw, micv_pf_destroy);
+        members.push_back(raw);
+        bboxWH.push_back(tr.bboxSize.width);
+        bboxWH.push_back(tr.bboxSize.height);
+    }
+    micv_pf_group *rawGroup = nullptr;
+    micv_shim::check(micv_pf_group_create(members.data(), static_cast<int>(count), &rawGroup));
+    std::shared_ptr<micv_pf_group> group(rawGroup, micv_pf_group_destroy);  // declared after the filters: destroyed first
+    std::vector<std::vector<int>> save(count);
+    std::vector<std::vector<Mat>> kept(count);
+    std::vector<std::vector<uint8_t *>> out(count);
+    std::vector<const int *> savePtr;
+    std::vector<uint8_t *const *> outPtr;
+    std::vector<int> nsave;
+    size_t ostride = 0;
+    for (size_t k = 0; k < count; k++) {
+        for (int t = 0; t < nframes; t++)
+            if (saveSets[k].count(t)) save[k].push_back(t);
+        kept[k].reserve(save[k].size());
+        for (size_t j = 0; j < save[k].size(); j++) {
+            kept[k].emplace_back(f0.rows, f0.cols, f0.type());
+            ostride = kept[k].back().step;
+            out[k].push_back(kept[k].back().data);
+        }
+        savePtr.push_back(save[k].data());
+        outPtr.push_back(out[k].data());
+        nsave.push_back(static_cast<int>(save[k].size()));
+    }
+    std::vector<micv_pf_state> flat((size_t)nframes * count);
+    micv_shim::check(micv_ps6_group_track_display_seq_host(group.get(), fp.data(), nframes, f0.step, kDotColor.val, bboxWH.data(),
+                                                           kBoxColor.v, savePtr.data(), nsave.data(), 0, outPtr.data(),
+                                                           ostride, flat.data()));
+    std::vector<std::vector<micv_pf_state>> states(count, std::vector<micv_pf_state>(nframes));
+    for (size_t k = 0; k < count; k++) {
+        for (int t = 0; t < nframes; t++) states[k][t] = flat[(size_t)t * count + k];
+        for (size_t j = 0; j < save[k].size(); j++) micv_viz::imwrite(framePath(prefixes[k], save[k][j], kept[k][j], ext), kept[k][j]);
     }
     return states;
 }
