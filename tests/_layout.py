@@ -12,7 +12,10 @@ placed in it
 Two departures, each for planes the header wants that way: `dense` drops the row padding only (pitch = cols elements;
 the base offset, the margins and the gap between the images of a batch stay), `tight` drops the gap between images.
 `packed=True` gives the layout the Python wrappers use instead (256-byte aligned, dense rows, dense images) inside the
-same kind of block, so the same check applies to both calls of the table test.
+same kind of block, so the same check applies to both calls of the table test.  A plane's own `packed` (True / False)
+overrides the block's: the mixed layouts of the driver table place the inputs one way and the outputs the other in
+ONE block, so that a kernel that keeps an alignment flag per plane meets an aligned source with an unaligned
+destination and the reverse.
 
 check(slab, outputs, expected) compares bytes as uint8 (NaN is not special) and names plane, image, row and column
 of the first byte that is wrong."""
@@ -33,9 +36,10 @@ class Plane:
     shape = (rows, cols) / (nimg, rows, cols) + dtype for an output that starts as sentinel.  cols counts ELEMENTS
     (interleaved channels included).  band = (r0, r1): an output of which only rows [r0, r1) may be written.
     dense: the header wants this plane without row padding (pad = 0); tight: the header wants the images of the batch
-    back to back (no gap).  Base offset and margins stay either way."""
+    back to back (no gap).  Base offset and margins stay either way.  packed: None = as the block, True / False = this
+    plane packed / embedded whatever the block is."""
 
-    def __init__(self, name, data=None, shape=None, dtype=None, pad=3, band=None, dense=False, tight=False):
+    def __init__(self, name, data=None, shape=None, dtype=None, pad=3, band=None, dense=False, tight=False, packed=None):
         if data is not None:
             data = np.ascontiguousarray(data)
             shape, dtype = data.shape, data.dtype
@@ -44,7 +48,7 @@ class Plane:
         self.nimg, self.rows, self.cols = (shape if self.batched else (1,) + tuple(shape))
         while not dense and (self.cols + pad) * self.dtype.itemsize % 16 == 0:
             pad += 2  # the smallest odd pad from `pad` up that keeps the pitch off a multiple of 16 bytes
-        self.pad, self.band, self.dense, self.tight = (0 if dense else pad), band, dense, tight
+        self.pad, self.band, self.dense, self.tight, self.packed = (0 if dense else pad), band, dense, tight, packed
         assert dense or pad % 2 == 1, "pad must be odd"
         # filled in by Slab
         self.base = self.pitch = self.dist = None
@@ -62,7 +66,7 @@ class Slab:
         off = MARGIN
         for p in planes:
             off = -(-off // 256) * 256
-            if packed:
+            if packed if p.packed is None else p.packed:
                 p.base, p.pitch = off, p.cols * p.item
                 p.dist = p.rows * p.pitch
             else:

@@ -61,6 +61,40 @@ def test_layout_rules():
     assert len(set(pat[:256].tolist())) == 256 and not np.array_equal(pat[:256], pat[256:512])
 
 
+def test_per_plane_packed_override():
+    """The mixed layouts of the driver table: one block, the inputs placed one way and the outputs the other.  The check
+    works on either kind of plane: a clean call passes, a store into the embedded plane's row padding is named, and so
+    is one behind the last row of the packed plane."""
+    rng = np.random.default_rng(8)
+    src = rng.integers(0, 256, (2, 9, 13)).astype(np.uint8)
+    for src_packed, dst_packed, block in ((True, False, False), (False, True, False), (True, False, True), (False, True, True)):
+        s = Y.slab([Y.Plane("src", data=src, packed=src_packed), Y.Plane("dst", shape=(2, 9, 13), dtype=np.uint8, packed=dst_packed)],
+                   packed=block, device="cpu")
+        for p, packed in ((s.planes["src"], src_packed), (s.planes["dst"], dst_packed)):
+            if packed:
+                assert p.base % 256 == 0 and p.pitch == 13 and p.dist == 9 * 13
+            else:
+                assert p.base % 256 == 1 and p.pitch == 13 + p.pad and p.pad % 2 == 1 and p.dist > 9 * p.pitch
+            assert p.base >= Y.MARGIN and s.nbytes - (p.base + p.nimg * p.dist) >= Y.MARGIN
+        assert np.array_equal(s.read("src"), src)
+        host = s.buf.numpy()
+        d = s.planes["dst"]
+        for i in range(2):
+            Y.Slab._rows(host, d, i)[:] = 255 - src[i]
+        Y.check(s, ["dst"], {"dst": 255 - src})
+        if dst_packed:
+            poke(s, "dst", 1, 9, 0)
+            with pytest.raises(AssertionError, match=r"margin behind plane 'dst' image 1 row 9 col 0 "):
+                Y.check(s, ["dst"], {"dst": 255 - src})
+        else:
+            poke(s, "dst", 0, 4, 13)
+            with pytest.raises(AssertionError, match=r"row padding of plane 'dst' image 0 row 4 col 13 "):
+                Y.check(s, ["dst"], {"dst": 255 - src})
+    # None follows the block
+    s = Y.slab([Y.Plane("a", shape=(4, 8), dtype=np.float32)], packed=True, device="cpu")
+    assert s.planes["a"].base % 256 == 0
+
+
 def test_clean_call_passes():
     s, src = make()
     good_call(s, src)
