@@ -722,6 +722,45 @@ int micv_generate_edge_f32_dev(micv_ctx *ctx, const float *src, int rows, int co
 int micv_generate_edge_f32_host(micv_ctx *ctx, const float *src, int rows, int cols, size_t stride, int gauss_size,
                                 double gauss_sigma, double low_thresh, double high_thresh, uint8_t *edges,
                                 size_t estride);
+
+/* ------------------------------ ps1: edges without a host wait, and a batch ------------------ */
+
+/* The entries above stop the host: their hysteresis is a loop of launches that ends when a polled word says so.  The
+ * `_async` entries below compute the same bytes with a FIXED sequence of launches, whatever the pixels are: the
+ * hysteresis is connected-component labelling of weak | strong with a lock-free union-find over horizontal runs of the
+ * bit planes (init, union, mark, emit: DESIGN.md "Hysteresis without the host").  No word is read on the host and no
+ * workgroup waits for another, so they ENQUEUE ON `stream` AND RETURN WITHOUT WAITING for the device; they may sit in a
+ * captured stream once the context's arena has the size (a first call of the shape outside the capture sees to that:
+ * growing the arena synchronises).  As everywhere in this library a context is used from one stream at a time: the arena
+ * is shared.  A refusal enqueues nothing.  rows * cols >= 2^31 is MICV_EINVAL (labels are 32-bit pixel indices).
+ * Scratch per image: rows * cols bytes (blur), 2 * rows * ceil(cols / 64) words (bit planes), 4 * rows * cols bytes (parents).
+ *
+ * micv_hysteresis_u8: the stage on its own.  cand and strong are byte masks, non-zero = set, each plane with its own pitch
+ * and any address; edges = 255 where the pixel lies in an 8-connected component of cand | strong that holds a strong
+ * pixel (a strong pixel outside cand counts), 0 elsewhere. */
+int micv_hysteresis_u8_async(micv_ctx *ctx, const uint8_t *cand, size_t cstride, const uint8_t *strong, size_t sstride, int rows,
+                             int cols, uint8_t *edges, size_t estride, micv_stream stream);
+int micv_hysteresis_u8_host(micv_ctx *ctx, const uint8_t *cand, size_t cstride, const uint8_t *strong, size_t sstride, int rows, int cols,
+                            uint8_t *edges, size_t estride);
+/* micv_generate_edge_dev / micv_generate_edge_f32_dev without the wait: the same arguments accepted and refused, the same
+ * bytes. */
+int micv_generate_edge_async(micv_ctx *ctx, const uint8_t *src, int rows, int cols, size_t stride, int gauss_size, double gauss_sigma,
+                             double low_thresh, double high_thresh, uint8_t *edges, size_t estride, micv_stream stream);
+int micv_generate_edge_f32_async(micv_ctx *ctx, const float *src, int rows, int cols, size_t stride, int gauss_size, double gauss_sigma,
+                                 double low_thresh, double high_thresh, uint8_t *edges, size_t estride, micv_stream stream);
+/* `batch` images of one size, image i at src + i * image_bytes, its edges at edges + i * edges_image_bytes: element i holds
+ * the bytes of micv_generate_edge_dev on image i.  The image is a grid dimension of every launch.  A batch whose scratch
+ * (above, per image) passes scratch_mb MiB (0 = 64) goes in pieces of as many images as fit, one at least, one after the
+ * other on the stream.  batch >= 1; the images of a batch must not overlap. */
+int micv_generate_edge_batch_async(micv_ctx *ctx, const uint8_t *src, int batch, size_t image_bytes, int rows, int cols, size_t stride,
+                                   int gauss_size, double gauss_sigma, double low_thresh, double high_thresh, uint8_t *edges,
+                                   size_t edges_image_bytes, size_t estride, int scratch_mb, micv_stream stream);
+/* The same on host memory: per-image pointers and pitches (cv::Mat ROIs go in as they are); one upload block, one batch
+ * call, one download block.  Synchronous, as every _host entry. */
+int micv_generate_edge_batch_host(micv_ctx *ctx, const uint8_t *const *srcs, const size_t *strides, int batch, int rows, int cols,
+                                  int gauss_size, double gauss_sigma, double low_thresh, double high_thresh, uint8_t *const *edges,
+                                  const size_t *estrides);
+
 /* cv::erode with cv::getStructuringElement(MORPH_ELLIPSE, Size(ksize, ksize)), main.cpp:246-248, :282-284; ksize odd,
  * 1..7.  Row i of the footprint (dy = i - r, r = ksize / 2) has half-width cvRound(r * sqrt((r*r - dy*dy) / r*r)), 0 when
  * r = 0; anchor at the centre; BORDER_CONSTANT with morphologyDefaultBorderValue(): a tap outside the image is FLT_MAX

@@ -180,6 +180,13 @@ SIGNATURES = {
     "micv_gaussian_blur_f32_host": (i32, [vp, vp, i32, i32, sz, i32, f64, vp, sz]),
     "micv_generate_edge_f32_dev": (i32, [vp, vp, i32, i32, sz, i32, f64, f64, f64, vp, sz, vp]),
     "micv_generate_edge_f32_host": (i32, [vp, vp, i32, i32, sz, i32, f64, f64, f64, vp, sz]),
+    # ps1 edges without a host wait (canny_uf.hip): the stage alone, the two chains, the batch
+    "micv_hysteresis_u8_async": (i32, [vp, vp, sz, vp, sz, i32, i32, vp, sz, vp]),
+    "micv_hysteresis_u8_host": (i32, [vp, vp, sz, vp, sz, i32, i32, vp, sz]),
+    "micv_generate_edge_async": (i32, [vp, vp, i32, i32, sz, i32, f64, f64, f64, vp, sz, vp]),
+    "micv_generate_edge_f32_async": (i32, [vp, vp, i32, i32, sz, i32, f64, f64, f64, vp, sz, vp]),
+    "micv_generate_edge_batch_async": (i32, [vp, vp, i32, sz, i32, i32, sz, i32, f64, f64, f64, vp, sz, sz, i32, vp]),
+    "micv_generate_edge_batch_host": (i32, [vp, vp, vp, i32, i32, i32, i32, f64, f64, f64, vp, vp]),
     "micv_erode_ellipse_f32_dev": (i32, [vp, vp, i32, i32, sz, i32, vp, sz, vp]),
     "micv_erode_ellipse_f32_host": (i32, [vp, vp, i32, i32, sz, i32, vp, sz]),
     "micv_erode_ellipse_u8_dev": (i32, [vp, vp, i32, i32, sz, i32, vp, sz, vp]),

@@ -1311,6 +1311,41 @@ int micv_generate_edge_f32_host(micv_ctx *ctx, const float *src, int rows, int c
                       });
 }
 
+int micv_hysteresis_u8_host(micv_ctx *ctx, const uint8_t *cand, size_t cstride, const uint8_t *strong, size_t sstride, int rows, int cols,
+                            uint8_t *edges, size_t estride) {
+    HostCall h(ctx, "micv_hysteresis_u8_host");
+    if (!h.ok()) return h.finish();
+    MICV_REQUIRE(cand && strong && edges && rows > 0 && cols > 0 && cstride >= (size_t)cols && sstride >= (size_t)cols && estride >= (size_t)cols,
+                 "micv_hysteresis_u8_host: bad argument");
+    uint8_t *dc = h.up<uint8_t>(cand, cstride, (size_t)cols, rows), *dst = h.up<uint8_t>(strong, sstride, (size_t)cols, rows);
+    uint8_t *de = h.alloc<uint8_t>((size_t)rows * cols);
+    if (!h.ok()) return h.finish();
+    MICV_TRY(micv_hysteresis_u8_async(ctx, dc, cols, dst, cols, rows, cols, de, cols, h.s));
+    h.down(edges, estride, de, (size_t)cols, rows);
+    return h.finish();
+}
+
+// The images of a batch arrive as they lie in host memory (ROIs with pitches of their own) and are packed into ONE
+// device block on the way up; one batch call; the edges come down from one block, each to its own rows.
+int micv_generate_edge_batch_host(micv_ctx *ctx, const uint8_t *const *srcs, const size_t *strides, int batch, int rows, int cols,
+                                  int gauss_size, double gauss_sigma, double low_thresh, double high_thresh, uint8_t *const *edges,
+                                  const size_t *estrides) {
+    HostCall h(ctx, "micv_generate_edge_batch_host");
+    if (!h.ok()) return h.finish();
+    MICV_REQUIRE(srcs && strides && edges && estrides && batch >= 1 && rows > 0 && cols > 0, "micv_generate_edge_batch_host: bad argument");
+    for (int i = 0; i < batch; i++)
+        MICV_REQUIRE(srcs[i] && edges[i] && strides[i] >= (size_t)cols && estrides[i] >= (size_t)cols,
+                     "micv_generate_edge_batch_host: image %d: null pointer or a pitch below the width", i);
+    const size_t n = (size_t)rows * cols;
+    uint8_t *ds = h.alloc<uint8_t>(n * batch), *de = h.alloc<uint8_t>(n * batch);
+    for (int i = 0; i < batch; i++) h.up_to(ds + i * n, srcs[i], strides[i], (size_t)cols, rows);
+    if (!h.ok()) return h.finish();
+    MICV_TRY(micv_generate_edge_batch_async(ctx, ds, batch, n, rows, cols, cols, gauss_size, gauss_sigma, low_thresh, high_thresh, de, n, cols,
+                                            0, h.s));
+    for (int i = 0; i < batch; i++) h.down(edges[i], estrides[i], de + i * n, (size_t)cols, rows);
+    return h.finish();
+}
+
 int micv_erode_ellipse_f32_host(micv_ctx *ctx, const float *src, int rows, int cols, size_t sstride, int ksize, float *dst,
                                 size_t dstride) {
     return image_host(ctx, "micv_erode_ellipse_f32_host", src, sstride, (size_t)cols * 4, dst, dstride, (size_t)cols * 4, rows, cols,

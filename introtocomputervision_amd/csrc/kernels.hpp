@@ -50,6 +50,9 @@ int launch_gauss_u8(hipStream_t s, const uint8_t *src, size_t stride, int rows, 
                     size_t dstride);
 int canny_from_u8(micv_ctx *ctx, hipStream_t s, const uint8_t *cin, size_t cstride, int rows, int cols, double low_thresh,
                   double high_thresh, unsigned long long *weak, unsigned long long *strong, uint8_t *edges, size_t estride);
+// ps1.hip: the float front end of micv_generate_edge_f32_dev -- the float blur and saturate_cast<uchar>(cvRound(v)) into a
+// byte plane (stride in bytes, a multiple of 4)
+int launch_gauss_f32_to_u8(hipStream_t s, const float *src, size_t stride, int rows, int cols, const Taps &t, uint8_t *dst, size_t dstride);
 // hough.hip: maxDist of Hough.cu:258-259
 size_t hough_diag(int rows, int cols);
 

@@ -222,6 +222,12 @@ static uint32_t bgr_word(const uint8_t *c) { return (uint32_t)c[0] | (uint32_t)c
 
 static bool gauss_ok(int n, double sigma) { return n >= 1 && n <= 31 && (n & 1) && sigma > 0; }
 
+int launch_gauss_f32_to_u8(hipStream_t s, const float *src, size_t stride, int rows, int cols, const Taps &t, uint8_t *dst, size_t dstride) {
+    gauss_f32_tiled_kernel<true><<<dim3(cdiv(cols, GF_TW), cdiv(rows, GF_TH)), 256, 0, s>>>(src, stride, rows, cols, t, dst, dstride);
+    MICV_LAUNCH_CHECK();
+    return MICV_OK;
+}
+
 }  // namespace micv
 
 using namespace micv;

@@ -78,9 +78,10 @@ def findLocalMaxima(accumulator, numPeaks, threshold, ctx=None, lazy=False):
     return peaks[:cnt.value]
 
 
-def generateEdge(image, gaussianSize, gaussianSigma, lowerThreshold, upperThreshold, ctx=None):
+def generateEdge(image, gaussianSize, gaussianSigma, lowerThreshold, upperThreshold, ctx=None, wait=True):
     """sol::generateEdge (ps1_cpp/src/Solution.cpp:21-47) on a 2-D uint8 CUDA tensor -> 255/0 edge
-    mask (Gaussian blur + Canny, aperture 3)."""
+    mask (Gaussian blur + Canny, aperture 3).  wait=False (tensors only) takes micv_generate_edge_async: the same
+    bytes from a fixed sequence of launches, enqueued on the current stream without a host wait."""
     if isinstance(image, np.ndarray):  # host-pointer entry point
         img = np.ascontiguousarray(image, np.uint8)
         if img.ndim != 2:
@@ -98,8 +99,62 @@ def generateEdge(image, gaussianSize, gaussianSigma, lowerThreshold, upperThresh
         raise ValueError("image: need a 2-D uint8 CUDA tensor with unit column stride")
     rows, cols = image.shape
     edges = torch.empty((rows, cols), dtype=torch.uint8, device=image.device)
-    check(lib.micv_generate_edge_dev(_ctx_for(image, ctx).handle, image.data_ptr(), rows, cols,
-                                     image.stride(0), int(gaussianSize), float(gaussianSigma),
-                                     float(lowerThreshold), float(upperThreshold), edges.data_ptr(), cols,
-                                     B.stream_of(image)))
+    entry = lib.micv_generate_edge_dev if wait else lib.micv_generate_edge_async
+    check(entry(_ctx_for(image, ctx).handle, image.data_ptr(), rows, cols,
+                image.stride(0), int(gaussianSize), float(gaussianSigma),
+                float(lowerThreshold), float(upperThreshold), edges.data_ptr(), cols,
+                B.stream_of(image)))
+    return edges
+
+
+def generateEdgeBatch(images, gaussianSize, gaussianSigma, lowerThreshold, upperThreshold, ctx=None, scratch_mb=0):
+    """sol::generateEdge on a batch of images of one size in one call, without a host wait: element i is
+    generateEdge(images[i], ...).  A [batch, rows, cols] uint8 CUDA tensor with unit column stride (any row and image
+    strides that do not make images overlap) goes to micv_generate_edge_batch_async and gives a tensor; a list of 2-D
+    uint8 numpy arrays (views with pitches of their own are fine) goes to micv_generate_edge_batch_host and gives a
+    [batch, rows, cols] array.  scratch_mb bounds the scratch of one piece of a device batch (0 = 64 MiB)."""
+    gauss = (int(gaussianSize), float(gaussianSigma), float(lowerThreshold), float(upperThreshold))
+    if B.is_dev(images):
+        import torch
+        if not (images.is_cuda and images.dim() == 3 and images.dtype == torch.uint8 and images.stride(2) == 1):
+            raise ValueError("images: need a [batch, rows, cols] uint8 CUDA tensor with unit column stride")
+        batch, rows, cols = images.shape
+        edges = torch.empty((batch, rows, cols), dtype=torch.uint8, device=images.device)
+        pitch = images.stride(1) if rows > 1 else cols
+        check(lib.micv_generate_edge_batch_async(_ctx_for(images, ctx).handle, images.data_ptr(), batch,
+                                                 images.stride(0) if batch > 1 else rows * pitch, rows, cols, pitch, *gauss,
+                                                 edges.data_ptr(), rows * cols, cols, int(scratch_mb), B.stream_of(images)))
+        return edges
+    imgs = list(images)
+    if not imgs or any(not isinstance(a, np.ndarray) or a.ndim != 2 or a.dtype != np.uint8 or a.shape != imgs[0].shape
+                       or a.strides[1] != 1 for a in imgs):
+        raise ValueError("images: need a uint8 CUDA tensor or a non-empty list of 2-D uint8 numpy arrays of one shape")
+    rows, cols = imgs[0].shape
+    out = np.empty((len(imgs), rows, cols), np.uint8)
+    n = len(imgs)
+    srcs = (C.c_void_p * n)(*[a.ctypes.data for a in imgs])
+    strides = (C.c_size_t * n)(*[a.strides[0] if rows > 1 else cols for a in imgs])
+    dsts = (C.c_void_p * n)(*[out[i].ctypes.data for i in range(n)])
+    dstrides = (C.c_size_t * n)(*[cols] * n)
+    from .match import _host_ctx
+    check(lib.micv_generate_edge_batch_host((ctx or _host_ctx()).handle, srcs, strides, n, rows, cols, *gauss, dsts, dstrides))
+    return out
+
+
+def hysteresis(cand, strong, ctx=None):
+    """The hysteresis stage on its own (micv_hysteresis_u8_*): two 2-D uint8 masks of one shape, non-zero = set -> 255
+    where the pixel lies in an 8-connected component of cand | strong that holds a strong pixel, 0 elsewhere.  CUDA
+    tensors are enqueued on the current stream without a host wait; numpy arrays take the host entry."""
+    B.check2d(cand, np.uint8, name="cand")
+    B.check2d(strong, np.uint8, name="strong")
+    if B.is_dev(cand) != B.is_dev(strong) or tuple(cand.shape) != tuple(strong.shape):
+        raise ValueError("cand and strong: need two masks of one shape, both tensors or both arrays")
+    rows, cols = cand.shape
+    edges = B.empty_like_shape(cand, (rows, cols), np.uint8)
+    c = _ctx_for(cand, ctx)
+    args = (c.handle, B.ptr(cand), B.stride_bytes(cand), B.ptr(strong), B.stride_bytes(strong), rows, cols, B.ptr(edges), cols)
+    if B.is_dev(cand):
+        check(lib.micv_hysteresis_u8_async(*args, B.stream_of(cand)))
+    else:
+        check(lib.micv_hysteresis_u8_host(*args))
     return edges

@@ -62,18 +62,19 @@ def gaussianBlur(image, gaussianSize, gaussianSigma, ctx=None):
     return out
 
 
-def generateEdge(image, gaussianSize, gaussianSigma, lowerThreshold, upperThreshold, ctx=None):
+def generateEdge(image, gaussianSize, gaussianSigma, lowerThreshold, upperThreshold, ctx=None, wait=True):
     """sol::generateEdge (Solution.cpp:21-47) -> 255 / 0 edge mask.  uint8 images go to hough.generateEdge; float32
-    images (main.cpp:98, :107) are blurred in float and converted with saturate_cast<uchar>(cvRound(v)) first."""
+    images (main.cpp:98, :107) are blurred in float and converted with saturate_cast<uchar>(cvRound(v)) first.
+    wait=False (tensors only): the `_async` entries, the same bytes without a host wait."""
     if _image(image) is np.uint8:
-        return _hough.generateEdge(image, gaussianSize, gaussianSigma, lowerThreshold, upperThreshold, ctx=ctx)
+        return _hough.generateEdge(image, gaussianSize, gaussianSigma, lowerThreshold, upperThreshold, ctx=ctx, wait=wait)
     rows, cols = image.shape
     edges = B.empty_like_shape(image, (rows, cols), np.uint8)
     c = _ctx_for(image, ctx)
     args = (c.handle, B.ptr(image), rows, cols, B.stride_bytes(image), int(gaussianSize), float(gaussianSigma),
             float(lowerThreshold), float(upperThreshold), B.ptr(edges), B.stride_bytes(edges))
     if B.is_dev(image):
-        check(lib.micv_generate_edge_f32_dev(*args, B.stream_of(image)))
+        check((lib.micv_generate_edge_f32_dev if wait else lib.micv_generate_edge_f32_async)(*args, B.stream_of(image)))
     else:
         check(lib.micv_generate_edge_f32_host(*args))
     return edges

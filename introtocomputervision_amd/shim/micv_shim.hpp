@@ -905,6 +905,30 @@ inline void generateEdge(const Mat &input, const int gaussianSize, const double 
                                                      upperThreshold, out.ptr<uint8_t>(), out.step));
     output = out;
 }
+// sol::generateEdge on several CV_8UC1 images of one size (ROIs with steps of their own included) in ONE
+// micv_generate_edge_batch_host call: outputs[i] holds the bytes sol::generateEdge gives on inputs[i].  Not in the
+// reference; the library's batch form of its first ps1 call.
+inline void generateEdgeBatch(const std::vector<Mat> &inputs, const int gaussianSize, const double gaussianSigma,
+                              const double lowerThreshold, const double upperThreshold, std::vector<Mat> &outputs) {
+    micv_shim::require(!inputs.empty(), "sol::generateEdgeBatch: no image");
+    std::vector<Mat> outs;
+    std::vector<const uint8_t *> srcs;
+    std::vector<uint8_t *> dsts;
+    std::vector<size_t> steps, osteps;
+    for (const Mat &m : inputs) {
+        micv_shim::require(m.type() == micv_shim::U8 && m.rows == inputs[0].rows && m.cols == inputs[0].cols,
+                           "sol::generateEdgeBatch: CV_8UC1 images of one size expected");
+        outs.emplace_back(m.rows, m.cols, micv_shim::U8);
+        srcs.push_back(m.ptr<uint8_t>());
+        steps.push_back(m.step);
+        dsts.push_back(outs.back().ptr<uint8_t>());
+        osteps.push_back(outs.back().step);
+    }
+    micv_shim::check(micv_generate_edge_batch_host(micv_shim::context(), srcs.data(), steps.data(), (int)inputs.size(), inputs[0].rows,
+                                                   inputs[0].cols, gaussianSize, gaussianSigma, lowerThreshold, upperThreshold, dsts.data(),
+                                                   osteps.data()));
+    outputs = outs;
+}
 // sol::gaussianBlur, Solution.h:21, Solution.cpp:49-61: the output has the input's type (CV_8UC1 or CV_32FC1)
 inline void gaussianBlur(const Mat &input, const int gaussianSize, const double gaussianSigma, Mat &output) {
     micv_shim::require(input.type() == micv_shim::U8 || input.type() == micv_shim::F32,
