@@ -279,6 +279,17 @@ int micv_gaussian_pyramid_dev(micv_ctx *ctx, const float *src, int rows, int col
                               int levels, float *const *dst_levels, micv_stream stream);
 int micv_gaussian_pyramid_host(micv_ctx *ctx, const float *src, int rows, int cols,
                                size_t sstride, int levels, float *const *dst_levels);
+/* The grey planes AND the Gaussian pyramids of a frame sequence in ONE launch that reads the frames once (what
+ * micv_lk_flow_seq_async runs in front of its level chain): nframes (1 .. 32768) device frames of one format, frame t at
+ * frames + t*frame_pitch bytes, rows `stride` bytes apart, in the formats of micv_to_gray_f32_dev (8-bit frames at any
+ * address and pitch; float frames 4-byte aligned).  gray + t*gray_pitch bytes receives frame t's dense grey plane (pitch
+ * cols) with the bytes of micv_to_gray_f32_dev; dst_levels[l] + t*rows_l*cols_l floats, l = 1 .. levels - 1, level l of
+ * its pyramid as micv_gaussian_pyramid_batch_dev lays it out and with its bytes (dst_levels[0] is not read: level 0 is
+ * the grey plane).  A lane takes four pixels with 16-byte accesses when cols % 4 == 0 and every address and pitch keeps
+ * the alignment, one pixel otherwise; the bytes are the same. */
+int micv_gray_pyramid_seq_async(micv_ctx *ctx, const void *frames, size_t frame_pitch, int nframes, int rows, int cols, size_t stride,
+                                int channels, int depth, int levels, float *gray, size_t gray_pitch, float *const *dst_levels,
+                                micv_stream stream);
 /* The Laplacian pyramid of sol::runProblem2, ps5_cpp/src/Solution.cpp:187-200 (SURVEY.md §8f row
  * N4): L_i = G_i - resize_if_smaller(pyrUp(G_{i+1})), L_{levels-1} = G_{levels-1}; level l is
  * (rows>>l) x (cols>>l), written densely at dst_levels[l].  Device-resident throughout. */
@@ -327,6 +338,30 @@ int micv_lk_flow_pyr_frames_host(micv_ctx *ctx, const void *prev, const void *ne
 int micv_lk_flow_seq_host(micv_ctx *ctx, const void *const *frames, int nframes, int rows, int cols, size_t stride,
                           int channels, int depth, int win, int levels, float *const *u, float *const *v,
                           size_t ostride);
+/* The same sequence on the DEVICE, all pairs as one batch.  frames: nframes (2 .. 32768) device frames of one format,
+ * frame t at frames + t*frame_pitch bytes, rows `stride` bytes apart; the formats of micv_to_gray_f32_dev (1, 3 or 4
+ * interleaved channels, MICV_DEPTH_8U or MICV_DEPTH_32F).  8-bit frames may have any address and any pitch; float frames
+ * need a 4-byte aligned address, stride and frame_pitch.  frame_pitch >= (rows - 1)*stride + cols*channels*elem.  Pair p
+ * is (frame p, frame p + 1); its fields are at u + p*opair_pitch and v + p*opair_pitch bytes, rows ostride bytes apart,
+ * and hold the bytes that micv_to_gray_f32_dev on frames p and p + 1 followed by micv_lk_flow_pyr_dev(win, levels)
+ * writes -- for every window, every level count that fits, and any max_pairs.
+ *   One launch (seq_gray_pyr_kernel, pyramid.hip) reads the frames once and writes every frame's grey plane and every
+ * level of its pyramid; the level chain then runs once for all pairs with `next` = `prev` one frame on, so a frame is
+ * converted and decimated once although it is `next` of one pair and `prev` of the following one.  Single-channel float
+ * frames are read where they lie (no grey plane).
+ *   max_pairs bounds the scratch: a sequence with more pairs runs as pieces of max_pairs pairs (0 = 8, the measured point
+ * of the batch) one after the other on the stream, piece i on frames [i*max_pairs, i*max_pairs + npairs_i]; the frame two
+ * pieces share is converted twice, and the bytes do not depend on the cut.  micv_lk_flow_seq_plan (host only, no device)
+ * returns that list: first_frame[i], npairs[i] for i < *npieces; a `cap` below the count gives MICV_EINVAL with the
+ * count in *npieces.
+ *   The call only enqueues on `stream`: nothing is read back, and the frames are not written.  A refusal enqueues
+ * nothing.  The build-shaping experiment options
+ * (MICV_OPT_LK_BUILD_OVERLAP, MICV_OPT_LK_DIRECT_LEVELS, MICV_OPT_LK_STREAM_GROUPS, MICV_OPT_LK_SPLIT) are NOT honoured
+ * here; the tile options the level launches read from the context pass through as everywhere. */
+int micv_lk_flow_seq_async(micv_ctx *ctx, const void *frames, size_t frame_pitch, int nframes, int rows, int cols,
+                           size_t stride, int channels, int depth, int win, int levels, int max_pairs, float *u, float *v,
+                           size_t opair_pitch, size_t ostride, micv_stream stream);
+int micv_lk_flow_seq_plan(int nframes, int max_pairs, int *first_frame, int *npairs, int cap, int *npieces);
 /* cv::resize(..., INTER_LINEAR) on f32 as used at OpticalFlow.cpp:149-150. */
 int micv_resize_linear_dev(micv_ctx *ctx, const float *src, int srows, int scols, size_t sstride,
                            float *dst, int drows, int dcols, size_t dstride, micv_stream stream);
@@ -1632,6 +1667,22 @@ int micv_dense_lk_display_dev(micv_ctx *ctx, const void *prev, const void *next,
 int micv_dense_lk_display_host(micv_ctx *ctx, const void *prev, const void *next, int rows, int cols, size_t stride, int channels,
                                int depth, int mode, int win, int levels, const uint8_t *color, float *u, float *v, size_t ostride,
                                uint8_t *arrows, size_t astride, uint8_t *jet_u, uint8_t *jet_v, size_t jstride);
+/* denseLKWrapper in pyramidal mode over consecutive frames (Solution.cpp:40-84 called as :254-285 does) as one call:
+ * nframes 8-bit device frames of 1 or 3 channels, laid out as micv_lk_flow_seq_async takes them.  Per pair p = (frame p,
+ * frame p + 1): u and v (at + p*opair_pitch bytes), the arrows on a copy of frame p (arrows + p*apitch, rows astride
+ * apart) and, when jet_u / jet_v are given, the JET maps of the normalised u and v (at + p*jpitch, rows jstride apart).
+ * On the device only: micv_lk_flow_seq_async (max_pairs 0), micv_gray_or_bgr_to_bgr8_dev per frame, ONE
+ * micv_draw_velocity_vectors_dev for all pairs, one micv_normalize_minmax_batch_dev for all u and one for all v.  Every
+ * output of pair p holds the bytes of micv_dense_lk_display_dev(MICV_LK_PYRAMIDAL) on frames p and p + 1.  A refusal
+ * enqueues nothing.  The _host form takes per-frame and per-pair host pointers with one stride each, as
+ * micv_lk_flow_seq_host does: one block of frames up, one call, one block of outputs down. */
+int micv_dense_lk_display_seq_async(micv_ctx *ctx, const void *frames, size_t frame_pitch, int nframes, int rows, int cols,
+                                    size_t stride, int channels, int depth, int win, int levels, const uint8_t *color, float *u,
+                                    float *v, size_t opair_pitch, size_t ostride, uint8_t *arrows, size_t apitch, size_t astride,
+                                    uint8_t *jet_u, uint8_t *jet_v, size_t jpitch, size_t jstride, micv_stream stream);
+int micv_dense_lk_display_seq_host(micv_ctx *ctx, const void *const *frames, int nframes, int rows, int cols, size_t stride, int channels,
+                                   int depth, int win, int levels, const uint8_t *color, float *const *u, float *const *v, size_t ostride,
+                                   uint8_t *const *arrows, size_t astride, uint8_t *const *jet_u, uint8_t *const *jet_v, size_t jstride);
 
 /* ------------------------------------------------------------------ ps4: driver ------ */
 /* What ProblemSets/ps4_cpp/src/Solution.cpp writes out between harris::, sift::, the matcher and ransac::, on the

@@ -111,6 +111,9 @@ SIGNATURES = {
     "micv_to_gray_f32_host": (i32, [vp, vp, i32, i32, sz, i32, i32, vp, sz]),
     "micv_lk_flow_pyr_frames_host": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, vp, vp, sz]),
     "micv_lk_flow_seq_host": (i32, [vp, C.POINTER(vp), i32, i32, i32, sz, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), sz]),
+    "micv_lk_flow_seq_async": (i32, [vp, vp, sz, i32, i32, i32, sz, i32, i32, i32, i32, i32, vp, vp, sz, sz, vp]),
+    "micv_lk_flow_seq_plan": (i32, [i32, i32, vp, vp, i32, vp]),
+    "micv_gray_pyramid_seq_async": (i32, [vp, vp, sz, i32, i32, i32, sz, i32, i32, i32, vp, sz, vp, vp]),
     "micv_resize_linear_dev": (i32, [vp, vp, i32, i32, sz, vp, i32, i32, sz, vp]),
     # ps4
     "micv_sobel_dev": (i32, [vp, vp, i32, i32, sz, i32, f32, vp, vp, sz, vp]),
@@ -212,6 +215,8 @@ SIGNATURES = {
     "micv_ps5_warp_diff_seq_host": (i32, [vp, C.POINTER(vp), i32, i32, i32, sz, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "micv_dense_lk_display_dev": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp, vp, sz, vp]),
     "micv_dense_lk_display_host": (i32, [vp, vp, vp, i32, i32, sz, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp, vp, sz]),
+    "micv_dense_lk_display_seq_async": (i32, [vp, vp, sz, i32, i32, i32, sz, i32, i32, i32, i32, vp, vp, vp, sz, sz, vp, sz, sz, vp, vp, sz, sz, vp]),
+    "micv_dense_lk_display_seq_host": (i32, [vp, vp, i32, i32, i32, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp, sz, vp, vp, sz]),
     # ps4 driver
     "micv_draw_dots_dev": (i32, [vp, vp, i32, i32, i32, sz, vp, sz, vp, sz, vp]),
     "micv_draw_dots_host": (i32, [vp, vp, i32, i32, i32, sz, vp, sz, vp, sz]),

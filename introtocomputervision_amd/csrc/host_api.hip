@@ -1598,6 +1598,47 @@ int micv_dense_lk_display_host(micv_ctx *ctx, const void *prev, const void *next
     return h.finish();
 }
 
+int micv_dense_lk_display_seq_host(micv_ctx *ctx, const void *const *frames, int nframes, int rows, int cols, size_t stride, int channels,
+                                   int depth, int win, int levels, const uint8_t *color, float *const *u, float *const *v, size_t ostride,
+                                   uint8_t *const *arrows, size_t astride, uint8_t *const *jet_u, uint8_t *const *jet_v, size_t jstride) {
+    HostCall h(ctx, "micv_dense_lk_display_seq_host");
+    if (!h.ok()) return h.finish();
+    MICV_REQUIRE(frames && color && u && v && arrows && nframes >= 2 && nframes <= 32768 && rows > 0 && cols > 0,
+                 "micv_dense_lk_display_seq_host: bad argument");
+    MICV_REQUIRE(depth == MICV_DEPTH_8U && (channels == 1 || channels == 3),
+                 "micv_dense_lk_display_seq_host: depth %d / %d channels not supported (8-bit frames of 1 or 3 channels)", depth, channels);
+    MICV_REQUIRE((jet_u == nullptr) == (jet_v == nullptr), "micv_dense_lk_display_seq_host: give both colour maps or none");
+    const size_t srb = (size_t)cols * channels, rb = (size_t)cols * 4, irb = (size_t)cols * 3;
+    MICV_REQUIRE(stride >= srb && stride_ok(ostride, cols, 4) && astride >= irb && (!jet_u || jstride >= irb),
+                 "micv_dense_lk_display_seq_host: bad stride");
+    const int pairs = nframes - 1;
+    for (int t = 0; t < nframes; t++) MICV_REQUIRE(frames[t] != nullptr, "micv_dense_lk_display_seq_host: frame %d is null", t);
+    for (int p = 0; p < pairs; p++)
+        MICV_REQUIRE(u[p] && v[p] && arrows[p] && (!jet_u || (jet_u[p] && jet_v[p])), "micv_dense_lk_display_seq_host: an output of pair %d is null", p);
+    // one block of frames up, one block of outputs down: [u | v | arrows | jet_u | jet_v], each pairs images of one pitch
+    const size_t fp = pitch256(srb * rows), op = pitch256(rb * rows), ip = pitch256(irb * rows);
+    char *df = h.alloc<char>(fp * nframes);
+    char *out = h.alloc<char>((2 * op + (jet_u ? 3 : 1) * ip) * pairs);
+    if (!h.ok()) return h.finish();
+    for (int t = 0; t < nframes; t++) h.up_to(df + t * fp, frames[t], stride, srb, rows);
+    if (!h.ok()) return h.finish();
+    float *du = reinterpret_cast<float *>(out), *dv = reinterpret_cast<float *>(out + op * pairs);
+    uint8_t *da = reinterpret_cast<uint8_t *>(out + 2 * op * pairs);
+    uint8_t *ju = jet_u ? da + ip * pairs : nullptr, *jv = jet_u ? ju + ip * pairs : nullptr;
+    MICV_TRY(micv_dense_lk_display_seq_async(ctx, df, fp, nframes, rows, cols, srb, channels, depth, win, levels, color, du, dv, op, rb, da, ip, irb,
+                                             ju, jv, ip, irb, h.s));
+    for (int p = 0; p < pairs; p++) {
+        h.down(u[p], ostride, reinterpret_cast<char *>(du) + p * op, rb, rows);
+        h.down(v[p], ostride, reinterpret_cast<char *>(dv) + p * op, rb, rows);
+        h.down(arrows[p], astride, da + p * ip, irb, rows);
+        if (jet_u) {
+            h.down(jet_u[p], jstride, ju + p * ip, irb, rows);
+            h.down(jet_v[p], jstride, jv + p * ip, irb, rows);
+        }
+    }
+    return h.finish();
+}
+
 // ---- ps4 driver (ps4.hip) ----------------------------------------------------------------------
 
 int micv_draw_dots_host(micv_ctx *ctx, const void *gray, int depth, int rows, int cols, size_t gstride, const float *corners,

@@ -32,6 +32,11 @@ int launch_pyr_build2(hipStream_t s, const float *src_a, const float *src_b, siz
                       int sstride, int rows, int cols, int levels, float *const *dst_a,
                       float *const *dst_b, int batch, const int *row_lo = nullptr,
                       const int *row_hi = nullptr);
+// A frame sequence (frame f at src + f*frame_pitch bytes, 1 / 3 / 4 channels of MICV_DEPTH_8U, 3 / 4 of MICV_DEPTH_32F):
+// the dense grey plane of every frame (gray + f*gray_elems, pitch cols) and levels 1 .. levels-1 of its pyramid
+// (dst[l] + f*rows_l*cols_l; dst[0] is not read) in one launch.
+int launch_seq_gray_pyr(hipStream_t s, const void *src, size_t frame_pitch, size_t sstride, int channels, int depth,
+                        int frames, int rows, int cols, float *gray, size_t gray_elems, int levels, float *const *dst);
 int launch_resize_linear(hipStream_t s, const float *src, int srows, int scols, int sstride,
                          float *dst, int drows, int dcols, int dstride);
 // du = resize(2 * pyrUp(du_coarse), drows x dcols) for `batch` pairs and both fields, one launch.

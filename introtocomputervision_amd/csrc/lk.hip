@@ -1157,6 +1157,104 @@ static int lk_pyr_batch(micv_ctx *ctx, hipStream_t s, const float *prev, const f
     return rc;
 }
 
+// lk::calcOpticalFlowPyr over one piece of a frame sequence: F frames, pairs (0, 1) .. (F - 2, F - 1).  A sequence is a
+// batch whose `next` is `prev` one frame on, at every level: the chain drivers read both through two base pointers and
+// ONE per-pair distance, so every frame's grey plane and pyramid is made once and serves as `next` of one pair and
+// `prev` of the following one.  ONE reserve, carved in this order: the grey planes (dense, each padded to 64 floats), the
+// pyramids (level l of frame f at pyr + lvl_off[l]*F + f*rows_l*cols_l: make_plan's layout with batch = F), the four flow
+// ping-pong blocks of the F - 1 pairs, then the generic path's temporaries.  Single-channel float frames have no grey
+// plane: level 0 is the caller's frames.  One group, no carried build, no direct levels, no split planes.
+static int lk_pyr_seq(micv_ctx *ctx, hipStream_t s, const void *frames, size_t frame_pitch, int F, int rows, int cols,
+                      size_t stride, int channels, int depth, int win, int levels, float *u, float *v,
+                      size_t opair_elems, int ostride, bool allow_fused) {
+    PyrPlan plan;
+    make_plan(rows, cols, levels, &plan);
+    const bool fused = allow_fused && lk_fused_supports(win);
+    const int nb = F - 1;
+    const size_t n0 = (size_t)rows * cols;
+    const size_t plane = (n0 + 63) & ~size_t(63);
+    const bool own_l0 = channels == 1 && depth == MICV_DEPTH_32F;  // level 0 is read where the caller put it
+    size_t total = (own_l0 ? 0 : Carver::need(plane * F, 4)) + Carver::need(plan.pyr_elems * F, 4) + Carver::need(plane * nb, 4) * 4;
+    // the generic path's warped frames and product / sum planes, at most 1 GiB of them per chain (lk_pyr_batch)
+    const size_t gen_pair_bytes = (n0 + lk_generic_scratch(rows, cols)) * sizeof(float);
+    const size_t gen_fit = (size_t(1) << 30) / gen_pair_bytes;
+    const int kGenChunk = gen_fit < 1 ? 1 : (gen_fit > 4096 ? 4096 : (int)gen_fit);
+    const int gen_nb = nb < kGenChunk ? nb : kGenChunk;
+    if (!fused) total += Carver::need(n0 * gen_nb, 4) + Carver::need(lk_generic_scratch(rows, cols) * gen_nb, 4);
+    void *base;
+    MICV_TRY(ctx->reserve(total, &base));
+    Carver carve(base);
+    float *gray = own_l0 ? nullptr : carve.take<float>(plane * F);
+    float *pyr = carve.take<float>(plan.pyr_elems * F);
+    float *fu[2] = {carve.take<float>(plane * nb), carve.take<float>(plane * nb)};
+    float *fv[2] = {carve.take<float>(plane * nb), carve.take<float>(plane * nb)};
+    float *pd[16];
+    pd[0] = nullptr;
+    for (int l = 1; l < levels; l++) pd[l] = pyr + plan.lvl_off[l] * F;
+    const float *l0 = gray;
+    size_t l0_frame = plane;
+    int l0_stride = cols;
+    if (own_l0) {
+        l0 = static_cast<const float *>(frames);
+        l0_frame = frame_pitch / 4;
+        l0_stride = (int)(stride / 4);
+        if (levels > 1) MICV_TRY(launch_pyr_build(s, l0, l0_frame, l0_stride, rows, cols, levels, pd, F));
+    } else {
+        MICV_TRY(launch_seq_gray_pyr(s, frames, frame_pitch, stride, channels, depth, F, rows, cols, gray, plane, levels, pd));
+    }
+    auto make_chain = [&](int b0, int cnb, bool profile) {
+        LkChain c;
+        c.s = s;
+        c.prev = l0 + b0 * l0_frame;
+        c.next = c.prev + l0_frame;
+        c.pair_elems = l0_frame;
+        c.stride = l0_stride;
+        for (int l = 1; l < levels; l++) {
+            c.ppyr[l] = pd[l] + (size_t)b0 * plan.rows[l] * plan.cols[l];
+            c.npyr[l] = c.ppyr[l] + (size_t)plan.rows[l] * plan.cols[l];
+        }
+        c.nb = cnb;
+        for (int i = 0; i < 2; i++) {
+            c.fu[i] = fu[i] + plane * b0;
+            c.fv[i] = fv[i] + plane * b0;
+        }
+        c.u = u + b0 * opair_elems;
+        c.v = v + b0 * opair_elems;
+        c.opair_elems = opair_elems;
+        c.ostride = ostride;
+        c.profile = profile;
+        return c;
+    };
+    if (!fused) {
+        ctx->prof_pairs = gen_nb;
+        float *warped = carve.take<float>(n0 * gen_nb);
+        float *gen = carve.take<float>(lk_generic_scratch(rows, cols) * gen_nb);
+        for (int b0 = 0; b0 < nb; b0 += kGenChunk)
+            MICV_TRY(lk_chain_generic(ctx, plan, make_chain(b0, nb - b0 < kGenChunk ? nb - b0 : kGenChunk, b0 == 0), win, warped, gen));
+        return MICV_OK;
+    }
+    ctx->prof_pairs = nb;
+    return lk_chain_fused(ctx, plan, make_chain(0, nb, true), win);
+}
+
+// The pieces of a sequence: piece i takes frames [i*m, i*m + npairs_i], m = max_pairs (0 = 8; at most the sequence's
+// pairs).  The one statement of the
+// rule: micv_lk_flow_seq_plan lists it and micv_lk_flow_seq_async walks it.
+static int seq_piece_pairs(int nframes, int max_pairs) {  // never more than the sequence has: no sum below can overflow
+    const int m = max_pairs ? max_pairs : 8;
+    return m < nframes - 1 ? m : nframes - 1;
+}
+static int seq_pieces(int nframes, int max_pairs) {
+    const int m = seq_piece_pairs(nframes, max_pairs);
+    return (nframes - 1 + m - 1) / m;
+}
+static void seq_piece(int nframes, int max_pairs, int i, int *first_frame, int *npairs) {
+    const int m = seq_piece_pairs(nframes, max_pairs);
+    const int left = nframes - 1 - i * m;
+    *first_frame = i * m;
+    *npairs = left < m ? left : m;
+}
+
 }  // namespace micv
 
 using namespace micv;
@@ -1193,6 +1291,52 @@ int micv_lk_flow_pyr_batch_dev(micv_ctx *ctx, const float *prev, const float *ne
     return lk_pyr_batch(ctx, static_cast<hipStream_t>(stream), prev, next, batch, pair_stride / 4,
                         rows, cols, (int)(stride / 4), win, levels, u, v, opair_stride / 4,
                         (int)(ostride / 4), !ctx->opt[MICV_OPT_LK_FORCE_GENERIC]);
+}
+
+int micv_lk_flow_seq_plan(int nframes, int max_pairs, int *first_frame, int *npairs, int cap, int *npieces) {
+    MICV_REQUIRE(npieces != nullptr, "micv_lk_flow_seq_plan: npieces is null");
+    MICV_REQUIRE(nframes >= 2 && nframes <= 32768, "micv_lk_flow_seq_plan: %d frames (2 .. 32768)", nframes);
+    MICV_REQUIRE(max_pairs >= 0, "micv_lk_flow_seq_plan: max_pairs %d is negative (0 = 8)", max_pairs);
+    const int n = seq_pieces(nframes, max_pairs);
+    *npieces = n;
+    MICV_REQUIRE(cap >= n && first_frame && npairs, "micv_lk_flow_seq_plan: %d pieces do not fit a list of %d", n, cap < 0 ? 0 : cap);
+    for (int i = 0; i < n; i++) seq_piece(nframes, max_pairs, i, first_frame + i, npairs + i);
+    return MICV_OK;
+}
+
+int micv_lk_flow_seq_async(micv_ctx *ctx, const void *frames, size_t frame_pitch, int nframes, int rows, int cols,
+                           size_t stride, int channels, int depth, int win, int levels, int max_pairs, float *u, float *v,
+                           size_t opair_pitch, size_t ostride, micv_stream stream) {
+    MICV_REQUIRE(ctx && frames && u && v, "micv_lk_flow_seq: null argument");
+    MICV_REQUIRE(u != v, "micv_lk_flow_seq: u and v are one buffer");
+    MICV_REQUIRE(nframes >= 2 && nframes <= 32768, "micv_lk_flow_seq: %d frames (2 .. 32768)", nframes);
+    MICV_REQUIRE(max_pairs >= 0, "micv_lk_flow_seq: max_pairs %d is negative (0 = 8)", max_pairs);
+    MICV_REQUIRE(rows > 0 && cols > 0 && rows <= 32767 && cols <= 32767, "micv_lk_flow_seq: bad size %dx%d", rows, cols);
+    MICV_REQUIRE(channels == 1 || channels == 3 || channels == 4, "micv_lk_flow_seq: %d channels (1, 3 or 4)", channels);
+    MICV_REQUIRE(depth == MICV_DEPTH_8U || depth == MICV_DEPTH_32F, "micv_lk_flow_seq: depth %d (MICV_DEPTH_8U or MICV_DEPTH_32F)", depth);
+    const size_t es = depth == MICV_DEPTH_8U ? 1 : 4, srb = (size_t)cols * channels * es;
+    MICV_REQUIRE(stride >= srb && stride < (size_t)1 << 32, "micv_lk_flow_seq: a stride of %zu bytes does not hold a row of %zu", stride, srb);
+    MICV_REQUIRE(frame_pitch >= (size_t)(rows - 1) * stride + srb, "micv_lk_flow_seq: a frame pitch of %zu bytes does not hold a frame",
+                 frame_pitch);
+    MICV_REQUIRE(es == 1 || ((reinterpret_cast<uintptr_t>(frames) | stride | frame_pitch) & 3) == 0,
+                 "micv_lk_flow_seq: float frames need 4-byte aligned address, stride and frame pitch");
+    MICV_REQUIRE(stride_ok(ostride, cols, 4) && opair_pitch % 4 == 0 &&
+                     (nframes == 2 || opair_pitch >= (size_t)(rows - 1) * ostride + (size_t)cols * 4),
+                 "micv_lk_flow_seq: bad output stride or pair pitch");
+    MICV_REQUIRE(win >= 1 && win <= kMaxWin && (win & 1), "micv_lk_flow_seq: window %d must be odd and <= %d", win, kMaxWin);
+    MICV_REQUIRE(levels >= 1 && levels <= 16 && (rows >> (levels - 1)) > 0 && (cols >> (levels - 1)) > 0,
+                 "micv_lk_flow_seq: %d levels do not fit a %dx%d image", levels, rows, cols);
+    MICV_HIP(hipSetDevice(ctx->device));
+    // the first piece is the largest: its reserve serves the others, which follow it on the stream
+    const int n = seq_pieces(nframes, max_pairs);
+    for (int i = 0; i < n; i++) {
+        int f0, np;
+        seq_piece(nframes, max_pairs, i, &f0, &np);
+        MICV_TRY(lk_pyr_seq(ctx, static_cast<hipStream_t>(stream), static_cast<const char *>(frames) + (size_t)f0 * frame_pitch, frame_pitch,
+                            np + 1, rows, cols, stride, channels, depth, win, levels, u + (size_t)f0 * (opair_pitch / 4),
+                            v + (size_t)f0 * (opair_pitch / 4), opair_pitch / 4, (int)(ostride / 4), !ctx->opt[MICV_OPT_LK_FORCE_GENERIC]));
+    }
+    return MICV_OK;
 }
 
 int micv_lk_flow_pyr_dev(micv_ctx *ctx, const float *prev, const float *next, int rows, int cols,

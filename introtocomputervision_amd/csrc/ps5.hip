@@ -346,4 +346,37 @@ int micv_dense_lk_display_dev(micv_ctx *ctx, const void *prev, const void *next,
     return micv_normalize_minmax_dev(ctx, v, MICV_DEPTH_32F, rows, cols, ostride, nullptr, 0, nullptr, 0, jet_v, jstride, nullptr, stream);
 }
 
+// denseLKWrapper in pyramidal mode over consecutive frames (Solution.cpp:254-285): the flows of all pairs from
+// micv_lk_flow_seq_async, the arrow pictures in one launch, the colour maps of all u and of all v in one batch each.
+int micv_dense_lk_display_seq_async(micv_ctx *ctx, const void *frames, size_t frame_pitch, int nframes, int rows, int cols,
+                                    size_t stride, int channels, int depth, int win, int levels, const uint8_t *color, float *u,
+                                    float *v, size_t opair_pitch, size_t ostride, uint8_t *arrows, size_t apitch, size_t astride,
+                                    uint8_t *jet_u, uint8_t *jet_v, size_t jpitch, size_t jstride, micv_stream stream) {
+    MICV_REQUIRE(ctx && frames && color && u && v && arrows, "micv_dense_lk_display_seq: null argument");
+    MICV_REQUIRE(depth == MICV_DEPTH_8U, "micv_dense_lk_display_seq: depth %d not supported (8-bit frames)", depth);
+    MICV_REQUIRE(channels == 1 || channels == 3, "micv_dense_lk_display_seq: %d channels not supported (1 or 3)", channels);
+    MICV_REQUIRE(nframes >= 2 && nframes <= 32768, "micv_dense_lk_display_seq: %d frames (2 .. 32768)", nframes);
+    const size_t irb = (size_t)cols * 3;
+    MICV_REQUIRE(draw::size_ok(rows, cols, kMaxSide) && astride >= irb && astride < (size_t)1 << 32 &&
+                     (nframes == 2 || apitch >= (size_t)(rows - 1) * astride + irb),
+                 "micv_dense_lk_display_seq: bad size %dx%d, arrow stride or arrow pitch", rows, cols);
+    MICV_REQUIRE((jet_u == nullptr) == (jet_v == nullptr) &&
+                     (!jet_u || (jstride >= irb && jstride < (size_t)1 << 32 && (nframes == 2 || jpitch >= (size_t)(rows - 1) * jstride + irb))),
+                 "micv_dense_lk_display_seq: give both colour maps or none, with a stride and a pitch that hold %d columns", cols);
+    MICV_REQUIRE(u != v && (!jet_u || jet_u != jet_v), "micv_dense_lk_display_seq: outputs alias");
+    // the rest of what a step below would refuse is refused by the first of them, before anything is enqueued
+    MICV_TRY(micv_lk_flow_seq_async(ctx, frames, frame_pitch, nframes, rows, cols, stride, channels, depth, win, levels, 0, u, v, opair_pitch,
+                                    ostride, stream));
+    const int pairs = nframes - 1;
+    for (int p = 0; p < pairs; p++)
+        MICV_TRY(micv_gray_or_bgr_to_bgr8_dev(ctx, static_cast<const char *>(frames) + (size_t)p * frame_pitch, depth, channels, rows, cols, stride,
+                                              arrows + (size_t)p * apitch, astride, stream));
+    MICV_TRY(micv_draw_velocity_vectors_dev(ctx, arrows, apitch, astride, u, v, opair_pitch, ostride, pairs, rows, cols, color, stream));
+    if (!jet_u) return MICV_OK;
+    MICV_TRY(micv_normalize_minmax_batch_dev(ctx, u, opair_pitch, MICV_DEPTH_32F, pairs, rows, cols, ostride, nullptr, 0, 0, nullptr, 0, 0, jet_u,
+                                             jpitch, jstride, nullptr, stream));
+    return micv_normalize_minmax_batch_dev(ctx, v, opair_pitch, MICV_DEPTH_32F, pairs, rows, cols, ostride, nullptr, 0, 0, nullptr, 0, 0, jet_v,
+                                           jpitch, jstride, nullptr, stream);
+}
+
 }  // extern "C"

@@ -471,6 +471,14 @@ __global__ __launch_bounds__(256) void rgb8_to_gray_kernel(const uint8_t *__rest
 //   8U : the fixed-point weights above (4-channel input ignores alpha), then convertTo(CV_32F);
 //   32F: cv::cvtColor's float path, (c0*0.299f + c1*0.587f) + c2*0.114f, unfused;
 //   1 channel: convertTo(CV_32F) only (exact for 8-bit, a copy for float).
+// The grey value of one pixel of three colour samples: the ONE place the arithmetic is written (to_gray_kernel and
+// seq_gray_pyr_kernel both call it, so a sequence's grey planes are to_gray's by construction).
+template <typename T>
+__device__ __forceinline__ float gray_of(T c0, T c1, T c2) {
+    if (sizeof(T) == 1) return (float)(((int)c0 * 4899 + (int)c1 * 9617 + (int)c2 * 1868 + (1 << 13)) >> 14);
+    return ((float)c0 * 0.299f + (float)c1 * 0.587f) + (float)c2 * 0.114f;
+}
+
 template <typename T, int CN>
 __global__ __launch_bounds__(256) void to_gray_kernel(const T *__restrict__ src, size_t sstride_bytes,
                                                        float *__restrict__ dst, int dstride, int rows,
@@ -482,12 +490,93 @@ __global__ __launch_bounds__(256) void to_gray_kernel(const T *__restrict__ src,
     float g;
     if (CN == 1) {
         g = (float)s[0];
-    } else if (sizeof(T) == 1) {
-        g = (float)(((int)s[0] * 4899 + (int)s[1] * 9617 + (int)s[2] * 1868 + (1 << 13)) >> 14);
     } else {
-        g = ((float)s[0] * 0.299f + (float)s[1] * 0.587f) + (float)s[2] * 0.114f;
+        g = gray_of<T>(s[0], s[1], s[2]);
     }
     dst[(size_t)y * dstride + x] = g;
+}
+
+// A frame sequence's grey planes AND every pyramid level of every frame in one launch (micv_lk_flow_seq_async, lk.hip):
+// pyr_build_vec_kernel's structure with a byte or colour source and a level-0 write, so the source is read once and the
+// F grey launches plus the build launch become one.  Grid (column blocks, rows / 4, frame); 256 threads = 4 rows x 64
+// lanes.  Frame f is read at src + f*frame_pitch bytes (rows sstride bytes apart), its grey plane is written densely
+// (pitch cols) at gray + f*gray_elems, and level l >= 1 at L.dst[l] + f*rows_l*cols_l.  No LDS, no atomics.
+//   VEC : a lane owns FOUR consecutive pixels, loaded as one dword (u8 x 1), three dwords (u8 x 3), one 16-byte load
+//         (u8 x 4) or three / four 16-byte loads (f32 x 3 / 4); one float4 to the grey plane; on an odd row pixels 1 and
+//         3 as one float2 to level 1, and from pixel 3 the walk to the deeper levels.  The launcher admits it only for
+//         cols % 4 == 0 and addresses and pitches that keep every one of these accesses aligned.
+//   else: one pixel per lane, any address, any pitch.
+template <typename T, int CN, bool VEC>
+__global__ __launch_bounds__(256) void seq_gray_pyr_kernel(const void *__restrict__ src, size_t frame_pitch, size_t sstride,
+                                                            float *__restrict__ gray, size_t gray_elems, int rows, int cols,
+                                                            PyrLevels L) {
+    const int f = blockIdx.z;
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int x0 = (VEC ? 4 : 1) * (blockIdx.x * 64 + (threadIdx.x & 63));
+    if (x0 >= cols || y >= rows) return;
+    const char *row = static_cast<const char *>(src) + (size_t)f * frame_pitch + (size_t)y * sstride;
+    float *g = gray + (size_t)f * gray_elems + (size_t)y * cols + x0;
+    float last;  // the pixel the deeper levels may take: x0 + 3 (VEC) or x0
+    if (VEC) {
+        float p[4];
+        if (sizeof(T) == 1) {
+            const uint32_t *w = reinterpret_cast<const uint32_t *>(row + (size_t)CN * x0);
+            if (CN == 1) {
+                const uint32_t a = w[0];
+#pragma unroll
+                for (int j = 0; j < 4; j++) p[j] = (float)(uint8_t)(a >> (8 * j));
+            } else if (CN == 3) {
+                const uint32_t a[3] = {w[0], w[1], w[2]};
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    uint8_t c[3];
+#pragma unroll
+                    for (int k = 0; k < 3; k++) c[k] = (uint8_t)(a[(3 * j + k) >> 2] >> (8 * ((3 * j + k) & 3)));
+                    p[j] = gray_of<uint8_t>(c[0], c[1], c[2]);
+                }
+            } else {
+                const uint4 a4 = *reinterpret_cast<const uint4 *>(w);
+                const uint32_t a[4] = {a4.x, a4.y, a4.z, a4.w};
+#pragma unroll
+                for (int j = 0; j < 4; j++) p[j] = gray_of<uint8_t>((uint8_t)a[j], (uint8_t)(a[j] >> 8), (uint8_t)(a[j] >> 16));
+            }
+        } else {
+            const float4 *w = reinterpret_cast<const float4 *>(row + (size_t)CN * 4 * x0);
+            float c[4 * CN];
+#pragma unroll
+            for (int k = 0; k < CN; k++) {
+                const float4 t = w[k];
+                c[4 * k] = t.x; c[4 * k + 1] = t.y; c[4 * k + 2] = t.z; c[4 * k + 3] = t.w;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) p[j] = CN == 1 ? c[j] : gray_of<float>(c[CN * j], c[CN * j + 1], c[CN * j + 2]);
+        }
+        *reinterpret_cast<float4 *>(g) = make_float4(p[0], p[1], p[2], p[3]);
+        if (!(y & 1) || L.n < 2) return;
+        // level-1 pixels (y1, x1) and (y1, x1 + 1): y is odd and below rows, cols is a multiple of 4 and x0 + 3 below it,
+        // so y1 < rows / 2 and x1 + 1 < cols / 2 -- no tail case
+        const int y1 = y >> 1, x1 = x0 >> 1;
+        float *d1 = L.dst[1] + (size_t)f * L.rows[1] * L.cols[1] + (size_t)y1 * L.cols[1] + x1;
+        *reinterpret_cast<float2 *>(d1) = make_float2(p[1], p[3]);
+        last = p[3];
+    } else {
+        const T *s = reinterpret_cast<const T *>(row) + (size_t)CN * x0;
+        last = CN == 1 ? (float)s[0] : gray_of<T>(s[0], s[1], s[2]);
+        g[0] = last;
+        if (!(y & 1) || !(x0 & 1) || L.n < 2) return;
+        const int y1 = y >> 1, x1 = x0 >> 1;
+        if (y1 >= L.rows[1] || x1 >= L.cols[1]) return;
+        L.dst[1][(size_t)f * L.rows[1] * L.cols[1] + (size_t)y1 * L.cols[1] + x1] = last;
+    }
+    // deeper levels: level-1 pixel (yy, xx) with yy and xx odd is level-2 pixel (yy / 2, xx / 2), and so on
+    int yy = y >> 1, xx = VEC ? (x0 >> 1) + 1 : x0 >> 1, ll = 1;
+    while (ll + 1 < L.n && (yy & 1) && (xx & 1)) {
+        yy >>= 1;
+        xx >>= 1;
+        ll++;
+        if (yy < L.rows[ll] && xx < L.cols[ll])
+            L.dst[ll][(size_t)f * L.rows[ll] * L.cols[ll] + (size_t)yy * L.cols[ll] + xx] = last;
+    }
 }
 
 // dst = a - b (dense a, b of pitch `cols`; dst strided).
@@ -636,6 +725,45 @@ int launch_pyr_build(hipStream_t s, const float *src, size_t img_elems, int sstr
                              batch, nullptr, nullptr);
 }
 
+// Grey planes and pyramids of `frames` frames in one launch (seq_gray_pyr_kernel).  The form is chosen here, from the
+// addresses and pitches: the kernel tests nothing.
+int launch_seq_gray_pyr(hipStream_t s, const void *src, size_t frame_pitch, size_t sstride, int channels, int depth,
+                        int frames, int rows, int cols, float *gray, size_t gray_elems, int levels, float *const *dst) {
+    PyrLevels L = {};
+    L.n = levels;
+    for (int l = 0; l < levels; l++) {
+        L.rows[l] = rows >> l;
+        L.cols[l] = cols >> l;
+        L.dst[l] = l ? dst[l] : nullptr;
+    }
+    const bool u8 = depth == MICV_DEPTH_8U;
+    // the widest access of a lane: a dword for u8 x 1 / x 3, 16 bytes otherwise
+    const uintptr_t need = (u8 && channels != 4) ? 3 : 15;
+    bool vec = (cols & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | frame_pitch | sstride) & need) == 0 &&
+               (reinterpret_cast<uintptr_t>(gray) & 15) == 0 && (gray_elems & 3) == 0;
+    for (int l = 1; l < levels && l < 2; l++) vec = vec && (reinterpret_cast<uintptr_t>(dst[l]) & 7) == 0;
+    const dim3 grid(cdiv(cols, vec ? 256 : 64), cdiv(rows, 4), frames);
+#define MICV_SEQ(T, CN)                                                                                                        \
+    do {                                                                                                                       \
+        if (vec)                                                                                                               \
+            seq_gray_pyr_kernel<T, CN, true><<<grid, 256, 0, s>>>(src, frame_pitch, sstride, gray, gray_elems, rows, cols, L); \
+        else                                                                                                                   \
+            seq_gray_pyr_kernel<T, CN, false><<<grid, 256, 0, s>>>(src, frame_pitch, sstride, gray, gray_elems, rows, cols, L); \
+    } while (0)
+    if (u8) {
+        if (channels == 1) MICV_SEQ(uint8_t, 1);
+        if (channels == 3) MICV_SEQ(uint8_t, 3);
+        if (channels == 4) MICV_SEQ(uint8_t, 4);
+    } else {
+        if (channels == 1) MICV_SEQ(float, 1);
+        if (channels == 3) MICV_SEQ(float, 3);
+        if (channels == 4) MICV_SEQ(float, 4);
+    }
+#undef MICV_SEQ
+    MICV_LAUNCH_CHECK();
+    return MICV_OK;
+}
+
 }  // namespace micv
 
 using namespace micv;
@@ -724,6 +852,29 @@ int micv_gaussian_pyramid_batch_dev(micv_ctx *ctx, const float *src, int batch, 
     MICV_HIP(hipSetDevice(ctx->device));
     return launch_pyr_build2(static_cast<hipStream_t>(stream), src, nullptr, image_stride / 4, (int)(sstride / 4),
                              rows, cols, levels, dst_levels, nullptr, batch, row_begin, row_end);
+}
+
+int micv_gray_pyramid_seq_async(micv_ctx *ctx, const void *frames, size_t frame_pitch, int nframes, int rows, int cols, size_t stride,
+                                int channels, int depth, int levels, float *gray, size_t gray_pitch, float *const *dst_levels,
+                                micv_stream stream) {
+    MICV_REQUIRE(ctx && frames && gray && dst_levels, "micv_gray_pyramid_seq: null argument");
+    MICV_REQUIRE(nframes >= 1 && nframes <= 32768 && rows > 0 && cols > 0 && rows <= 32767 && cols <= 32767,
+                 "micv_gray_pyramid_seq: bad size: %d frames of %dx%d", nframes, rows, cols);
+    MICV_REQUIRE(channels == 1 || channels == 3 || channels == 4, "micv_gray_pyramid_seq: %d channels (1, 3 or 4)", channels);
+    MICV_REQUIRE(depth == MICV_DEPTH_8U || depth == MICV_DEPTH_32F, "micv_gray_pyramid_seq: depth %d (MICV_DEPTH_8U or MICV_DEPTH_32F)", depth);
+    const size_t es = depth == MICV_DEPTH_8U ? 1 : 4, srb = (size_t)cols * channels * es;
+    MICV_REQUIRE(stride >= srb && (nframes == 1 || frame_pitch >= (size_t)(rows - 1) * stride + srb),
+                 "micv_gray_pyramid_seq: the stride or the frame pitch is smaller than a row or a frame");
+    MICV_REQUIRE(es == 1 || ((reinterpret_cast<uintptr_t>(frames) | stride | frame_pitch) & 3) == 0,
+                 "micv_gray_pyramid_seq: float frames need 4-byte aligned address, stride and frame pitch");
+    MICV_REQUIRE(gray_pitch % 4 == 0 && (nframes == 1 || gray_pitch >= (size_t)rows * cols * 4),
+                 "micv_gray_pyramid_seq: the grey planes' pitch is smaller than a plane");
+    MICV_REQUIRE(levels >= 1 && levels <= 16 && (rows >> (levels - 1)) > 0 && (cols >> (levels - 1)) > 0,
+                 "micv_gray_pyramid_seq: %d levels do not fit a %dx%d image", levels, rows, cols);
+    for (int l = 1; l < levels; l++) MICV_REQUIRE(dst_levels[l] != nullptr, "micv_gray_pyramid_seq: dst_levels[%d] is null", l);
+    MICV_HIP(hipSetDevice(ctx->device));
+    return launch_seq_gray_pyr(static_cast<hipStream_t>(stream), frames, frame_pitch, stride, channels, depth, nframes, rows, cols, gray,
+                               gray_pitch / 4, levels, dst_levels);
 }
 
 int micv_laplacian_pyramid_dev(micv_ctx *ctx, const float *src, int rows, int cols,

@@ -200,3 +200,57 @@ def calcOpticalFlowPyrBatch(prev, next_, winSize=21, levels=4, ctx=None, out=Non
                                          int(levels), u.data_ptr(), v.data_ptr(), rows * cols * 4,
                                          cols * 4, stream))
     return u, v
+
+
+def sequencePlan(nframes, max_pairs=0):
+    """The pieces calcOpticalFlowPyrSequenceDevice cuts a sequence into (micv_lk_flow_seq_plan; no GPU needed): a list of
+    (first_frame, npairs); piece i runs on frames first_frame .. first_frame + npairs.  max_pairs = 0 means 8."""
+    import ctypes as C
+    n = C.c_int(0)
+    lib.micv_lk_flow_seq_plan(int(nframes), int(max_pairs), None, None, 0, C.byref(n))  # the count (refusals are raised below)
+    cap = max(n.value, 1)
+    first, pairs = (C.c_int * cap)(), (C.c_int * cap)()
+    check(lib.micv_lk_flow_seq_plan(int(nframes), int(max_pairs), first, pairs, cap, C.byref(n)))
+    return [(first[i], pairs[i]) for i in range(n.value)]
+
+
+def calcOpticalFlowPyrSequenceDevice(frames, winSize=21, levels=4, max_pairs=0, out=None, ctx=None, stream=None):
+    """lk::calcOpticalFlowPyr over a device-resident frame sequence, all pairs as one batch (micv_lk_flow_seq_async).
+    `frames`: a CUDA tensor [F, rows, cols] or [F, rows, cols, cn] (cn = 1, 3 or 4), uint8 or float32; the frame and row
+    strides are taken from the tensor (pixels must be dense).  One launch converts every frame to grey and builds every
+    level of its pyramid, then the level chain runs once for all F - 1 pairs.  More than `max_pairs` pairs (0 = 8) run as
+    pieces (sequencePlan).  Returns (u, v) as [F - 1, rows, cols] float32 tensors (`out`, when given), byte-identical to
+    the per-pair grey conversion + calcOpticalFlowPyr.  Nothing synchronises."""
+    import torch
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dim() in (3, 4) and frames.dtype in (torch.uint8, torch.float32)):
+        raise ValueError("frames: need a [F, rows, cols] or [F, rows, cols, cn] uint8 or float32 CUDA tensor")
+    nf, rows, cols = (int(d) for d in frames.shape[:3])
+    cn = int(frames.shape[3]) if frames.dim() == 4 else 1
+    es = frames.element_size()
+    st = [s * es for s in frames.stride()]
+    if nf < 2 or rows < 1 or cols < 1 or cn not in (1, 3, 4):
+        raise ValueError("frames: at least two non-empty frames of 1, 3 or 4 channels expected")
+    if (cols > 1 and st[2] != cn * es) or (frames.dim() == 4 and cn > 1 and st[3] != es):
+        raise ValueError("frames: need interleaved channels and dense pixels")
+    row = st[1] if rows > 1 else cols * cn * es
+    if row < cols * cn * es or st[0] < (rows - 1) * row + cols * cn * es:
+        raise ValueError("frames: rows or frames overlap")
+    shape = (nf - 1, rows, cols)
+    if out is None:
+        u = torch.empty(shape, dtype=torch.float32, device=frames.device)
+        v = torch.empty(shape, dtype=torch.float32, device=frames.device)
+    else:
+        u, v = out
+        for t, name in ((u, "out[0]"), (v, "out[1]")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == frames.device and t.dtype == torch.float32
+                    and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"{name}: must be a contiguous float32 CUDA tensor of shape {shape} on the frames' device")
+        if u.data_ptr() == v.data_ptr():
+            raise ValueError("out: u and v must be two different buffers")
+    if stream is None:
+        stream = torch.cuda.current_stream(frames.device).cuda_stream
+    c = ctx if ctx is not None else default_context(frames.device.index or 0, stream)
+    check(lib.micv_lk_flow_seq_async(c.handle, frames.data_ptr(), st[0], nf, rows, cols, row, cn, 0 if frames.dtype == torch.uint8 else 5,
+                                     int(winSize), int(levels), int(max_pairs), u.data_ptr(), v.data_ptr(), rows * cols * 4, cols * 4,
+                                     stream))
+    return u, v

@@ -226,3 +226,59 @@ def denseLKDisplay(prevImg, nextImg, mode="naive", winSize=21, levels=4, color=G
     else:
         check(lib.micv_dense_lk_display_host(*args))
     return (uv[0], uv[1], arrows) + ((jet[0], jet[1]) if colorMaps else ())
+
+
+def denseLKDisplaySequence(frames, winSize=21, levels=4, color=GREEN, colorMaps=True, ctx=None):
+    """denseLKWrapper in pyramidal mode over consecutive frames (Solution.cpp:254-285) as one call
+    (micv_dense_lk_display_seq_async / _host): 8-bit frames of 1 or 3 channels, a CUDA tensor [F, rows, cols(, 3)] or a
+    sequence of equal numpy frames.  Returns a dictionary of [F - 1, ...] arrays: "u", "v", "arrows" and, with colorMaps,
+    "uColorMap", "vColorMap"; pair p holds the bytes of denseLKDisplay(frames[p], frames[p + 1], "pyramidal")."""
+    dev = B.is_dev(frames)
+    if dev:
+        if len(frames.shape) not in (3, 4) or frames.shape[0] < 2:
+            raise ValueError("frames: need [F, rows, cols] or [F, rows, cols, 3] with F >= 2")
+        rows, cols, cn, depth, pitch = _frame(frames[0], "frames")
+        nf = int(frames.shape[0])
+        fpitch = frames.stride(0) * frames.element_size()
+        if fpitch < (rows - 1) * pitch + cols * cn:
+            raise ValueError("frames: frames overlap")
+        first = frames
+    else:
+        fs = [np.ascontiguousarray(f) for f in frames]
+        if len(fs) < 2 or any(f.shape != fs[0].shape or f.dtype != fs[0].dtype for f in fs):
+            raise ValueError("frames: at least two equal-shape frames expected")
+        rows, cols, cn, depth, pitch = _frame(fs[0], "frames")
+        nf = len(fs)
+        first = fs[0]
+    n = nf - 1
+    uv = B.empty_like_shape(first, (2, n, rows, cols))
+    arrows = B.empty_like_shape(first, (n, rows, cols, 3), np.uint8)
+    jet = B.empty_like_shape(first, (2, n, rows, cols, 3), np.uint8) if colorMaps else None
+    h = _ctx_for(first, ctx).handle
+    if dev:
+        check(lib.micv_dense_lk_display_seq_async(h, B.ptr(frames), fpitch, nf, rows, cols, pitch, cn, depth, int(winSize), int(levels),
+                                                  _color(color), B.ptr(uv[0]), B.ptr(uv[1]), rows * cols * 4, cols * 4, B.ptr(arrows),
+                                                  rows * cols * 3, cols * 3, B.ptr(jet[0]) if colorMaps else None,
+                                                  B.ptr(jet[1]) if colorMaps else None, rows * cols * 3, cols * 3, B.stream_of(frames)))
+    else:
+        def ptrs(a):
+            return (vp * n)(*[a[p].ctypes.data for p in range(n)])
+        check(lib.micv_dense_lk_display_seq_host(h, (vp * nf)(*[f.ctypes.data for f in fs]), nf, rows, cols, pitch, cn, depth, int(winSize),
+                                                 int(levels), _color(color), ptrs(uv[0]), ptrs(uv[1]), cols * 4, ptrs(arrows), cols * 3,
+                                                 ptrs(jet[0]) if colorMaps else None, ptrs(jet[1]) if colorMaps else None, cols * 3))
+    out = {"u": uv[0], "v": uv[1], "arrows": arrows}
+    if colorMaps:
+        out["uColorMap"], out["vColorMap"] = jet[0], jet[1]
+    return out
+
+
+def runProblem4(yosemite, pupper, winSize=21, levels=4, color=GREEN, ctx=None):
+    """sol::runProblem4 (Solution.cpp:248-290) without the files: the two frame sets (each three 8-bit frames, or any
+    sequence denseLKDisplaySequence takes) from two calls.  Returns {"ps5-4-a-1", "ps5-4-a-2", "ps5-4-b-1", "ps5-4-b-2"} ->
+    the arrow picture of pairs (0, 1) and (1, 2) of the first and of the second set, plus "flows": the two dictionaries."""
+    a = denseLKDisplaySequence(yosemite, winSize, levels, color, True, ctx)
+    b = denseLKDisplaySequence(pupper, winSize, levels, color, True, ctx)
+    if len(a["arrows"]) < 2 or len(b["arrows"]) < 2:
+        raise ValueError("runProblem4: three frames per set expected")
+    return {"ps5-4-a-1": a["arrows"][0], "ps5-4-a-2": a["arrows"][1], "ps5-4-b-1": b["arrows"][0], "ps5-4-b-2": b["arrows"][1],
+            "flows": (a, b)}

@@ -127,3 +127,28 @@ def rgb8ToGray(rgb, ctx=None):
                                         dst.data_ptr(), cols * 4,
                                         torch.cuda.current_stream(rgb.device).cuda_stream))
     return dst
+
+
+def grayPyramidSequence(frames, levels, ctx=None):
+    """The grey planes and the Gaussian pyramids of a device-resident frame sequence in ONE launch that reads the frames
+    once (micv_gray_pyramid_seq_async).  `frames`: a CUDA tensor [F, rows, cols] or [F, rows, cols, cn] (cn = 1, 3 or 4),
+    uint8 or float32, dense pixels, any frame and row stride.  Returns the list of levels: level 0 the [F, rows, cols] grey
+    planes (toGray's bytes), level l the [F, rows >> l, cols >> l] decimations (makeGaussianPyramid's bytes)."""
+    import torch
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dim() in (3, 4) and frames.dtype in (torch.uint8, torch.float32)):
+        raise ValueError("frames: need a [F, rows, cols] or [F, rows, cols, cn] uint8 or float32 CUDA tensor")
+    nf, rows, cols = (int(d) for d in frames.shape[:3])
+    cn = int(frames.shape[3]) if frames.dim() == 4 else 1
+    es = frames.element_size()
+    st = [s * es for s in frames.stride()]
+    if nf < 1 or rows < 1 or cols < 1 or cn not in (1, 3, 4):
+        raise ValueError("frames: non-empty frames of 1, 3 or 4 channels expected")
+    if (cols > 1 and st[2] != cn * es) or (frames.dim() == 4 and cn > 1 and st[3] != es):
+        raise ValueError("frames: need interleaved channels and dense pixels")
+    row = st[1] if rows > 1 else cols * cn * es
+    outs = [torch.empty((nf, rows >> l, cols >> l), dtype=torch.float32, device=frames.device) for l in range(int(levels))]
+    arr = (vp * len(outs))(*[o.data_ptr() for o in outs])
+    check(lib.micv_gray_pyramid_seq_async(_ctx_for(frames, ctx).handle, frames.data_ptr(), st[0], nf, rows, cols, row, cn,
+                                          0 if es == 1 else 5, int(levels), outs[0].data_ptr(), rows * cols * 4, arr,
+                                          torch.cuda.current_stream(frames.device).cuda_stream))
+    return outs

@@ -622,4 +622,55 @@ inline std::vector<std::pair<Mat, Mat>> denseLKSequenceDevice(const std::vector<
     return out;
 }
 
+// denseLKSequenceDevice as ONE library call (micv_dense_lk_display_seq_host): the frames go up as one block, the flows of
+// all pairs run as one batch on the frames' grey planes and pyramids (each made once), and u, v, the arrow pictures and
+// the colour maps come back as one block.  8-bit frames of 1 or 3 channels.  Same files, same bytes.
+inline std::vector<std::pair<Mat, Mat>> denseLKSequenceOneCall(const std::vector<Mat> &frames, const size_t windowSize,
+                                                               const std::string &filePrefix, const std::string &outputImg,
+                                                               bool saveColorMaps = true, const std::string &ext = ".ppm") {
+    micv_shim::require(frames.size() >= 2, "denseLKSequence: at least two frames expected");
+    const Mat &f0 = frames[0];
+    std::vector<const void *> fp;
+    for (const Mat &f : frames) {
+        micv_shim::require(f.rows == f0.rows && f.cols == f0.cols && f.type() == f0.type() && f.step == f0.step,
+                           "denseLKSequence: frames of one size, type and row pitch expected");
+        fp.push_back(f.data);
+    }
+    const size_t pairs = frames.size() - 1;
+    const int rows = f0.rows, cols = f0.cols;
+    const size_t n = (size_t)rows * cols;
+    std::vector<unsigned char> img(pairs * n * 3), jet(saveColorMaps ? 2 * pairs * n * 3 : 0);
+    std::vector<Mat> u, v;
+    std::vector<float *> up, vp;
+    std::vector<unsigned char *> ap, jup, jvp;
+    for (size_t p = 0; p < pairs; p++) {
+        u.emplace_back(rows, cols, micv_shim::F32);
+        v.emplace_back(rows, cols, micv_shim::F32);
+        up.push_back(u[p].ptr<float>(0));
+        vp.push_back(v[p].ptr<float>(0));
+        ap.push_back(&img[p * n * 3]);
+        if (saveColorMaps) {
+            jup.push_back(&jet[2 * p * n * 3]);
+            jvp.push_back(&jet[(2 * p + 1) * n * 3]);
+        }
+    }
+    unsigned char c[3];
+    color_bytes(Scalar(0, 255, 0, 255), c);
+    micv_shim::check(micv_dense_lk_display_seq_host(micv_shim::context(), fp.data(), (int)frames.size(), rows, cols, f0.step, f0.channels(),
+                                                    micv_shim::depth_code(f0), (int)windowSize, 4, c, up.data(), vp.data(), u[0].step, ap.data(),
+                                                    (size_t)cols * 3, saveColorMaps ? jup.data() : nullptr,
+                                                    saveColorMaps ? jvp.data() : nullptr, (size_t)cols * 3));
+    std::vector<std::pair<Mat, Mat>> out;
+    for (size_t p = 0; p < pairs; p++) {
+        const std::string name = outputImg + std::to_string(p);
+        imwrite(filePrefix + "/" + name + ext, Mat(rows, cols, micv::CV_8UC3, ap[p]));
+        if (saveColorMaps) {
+            imwrite(filePrefix + "/" + name + "-uColorMap" + ext, Mat(rows, cols, micv::CV_8UC3, jup[p]));
+            imwrite(filePrefix + "/" + name + "-vColorMap" + ext, Mat(rows, cols, micv::CV_8UC3, jvp[p]));
+        }
+        out.emplace_back(u[p], v[p]);
+    }
+    return out;
+}
+
 }  // namespace micv_viz
